@@ -16,7 +16,15 @@ P = 98,562 Gaussians, interaction-aware attribute blend on, RGB colours, 512x334
 
 Rank 0 prints ONE JSON line. Inputs are resident in HBM before the timed region starts. The timed steps replay one
 captured step (forward + loss + backward) from a HIP graph (`--no-graph`: kernel-by-kernel enqueue); collectives stay
-outside the graph; stage times for the roofline object come from eager steps with HIP events right after the timed region.
+outside the graph.
+
+A plain run sets up, warms up, times exactly --steps steps, writes the outputs of the last timed step if --dump-outputs DIR
+is given, and prints the line (`value`, `ms_per_step`, ...; `roofline` and `cpu_baseline` are null). `--full` adds what
+the headline figure does not need: repeat windows (--repeats, default 5), the per-step HIP-event spread, stage times for
+the roofline object (eager steps with HIP events right after the timed region), the instance count of the 3-sigma
+rects, the reference protocol's per-view cost and the CPU baseline.
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 from __future__ import annotations
 
@@ -36,6 +44,8 @@ HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0
 
 
 WARM_MS = 40.0        # minimum duration of the untimed graph-replay warm-up (see main)
+DUMP_MAX_BYTES = 64 * 10**6    # --dump-outputs: budget of all written files together (1 MiB of it kept for the .npy headers)
+DUMP_WHOLE_NUMEL = 1 << 16     # --dump-outputs: arrays up to this size are always written whole
 
 
 def algorithmic_bytes(P, NV, H, W, D, C=12, M=0):
@@ -290,6 +300,35 @@ def self_launch(n: int) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+def snapshot_outputs(arrays):
+    """Host float32 copies of `arrays` (name -> device tensor) within DUMP_MAX_BYTES. Arrays of at most DUMP_WHOLE_NUMEL
+    elements are kept whole; if the rest does not fit, each larger array is replaced by a fixed, seeded sample of its flat
+    elements (one element from each of n equal strata, n proportional to its size), the same elements on every run."""
+    arrays = {k: v.detach() for k, v in arrays.items() if v is not None}
+    limit = (DUMP_MAX_BYTES - (1 << 20)) // 4
+    total = sum(v.numel() for v in arrays.values())
+    big = sorted(k for k, v in arrays.items() if v.numel() > DUMP_WHOLE_NUMEL)
+    budget = limit - sum(v.numel() for k, v in arrays.items() if k not in big)
+    big_numel = sum(arrays[k].numel() for k in big)
+    out = {}
+    for k, v in arrays.items():
+        if total > limit and k in big:
+            n = max(1, v.numel() * budget // big_numel)
+            stride = v.numel() // n
+            g = torch.Generator().manual_seed(big.index(k) + 1)
+            idx = torch.arange(n, dtype=torch.int64) * stride + torch.randint(0, stride, (n,), generator=g)
+            v = v.reshape(-1)[idx.to(v.device)]
+        out[k] = v.float().cpu().numpy()
+    return out
+
+
+def write_outputs(out_dir, snap):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in snap.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -327,10 +366,20 @@ def main():
     ap.add_argument("--pipeline", type=int, default=1,
                     help="EXPERIMENT: capture this many copies of the step on as many streams and replay them round-robin, so that "
                          "consecutive (independent) steps overlap on the GPU; 1 = steps strictly one after the other (the contract's default)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed windows of --steps steps each; `value` / `ms_per_step` are the FIRST window's (the contract's exactly-K "
-                         "steps), the others are reported as repeat statistics")
+                         "steps), the others are reported as repeat statistics (default: 5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: repeat windows, the per-step spread, stage times and "
+                         "the roofline, the 3-sigma instance count, the reference protocol's per-view cost and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller (loss, image, radii, grad_<leaf>) as DIR/<name>.npy, float32; "
+                         f"at most {DUMP_MAX_BYTES // 10**6} MB in all, larger arrays as a fixed seeded sample of their flat elements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (the driver's own torchrun line, as CHILD
@@ -415,12 +464,22 @@ def main():
             p.grad = None
         # render + loss as one autograd node: mean|img - gt| and dL/dimg from one fused pass (gh_l1_loss), dL/dloss applied
         # inside the render backward (GhGrads.upstream_scale) instead of in an elementwise pass over the images
-        loss, _img, _ = rendered_l1_loss(cams, params["xyz"], params["opacity"], params["scaling"], params["rotation"],
-                                         params["shs"], gt, H=H, W=W, use_rgb=s.use_rgb, sh_degree=s.sh_degree, sync=sync,
-                                         xyz_b=params.get("xyz_b"), opacity_b=params.get("opacity_b"),
-                                         color_w=params.get("color_w"), color_b=params.get("color_b"),
-                                         defer_loss=defer_loss and args.defer_loss == "on", **pv)
+        loss, img, radii = rendered_l1_loss(cams, params["xyz"], params["opacity"], params["scaling"], params["rotation"],
+                                            params["shs"], gt, H=H, W=W, use_rgb=s.use_rgb, sh_degree=s.sh_degree, sync=sync,
+                                            xyz_b=params.get("xyz_b"), opacity_b=params.get("opacity_b"),
+                                            color_w=params.get("color_w"), color_b=params.get("color_b"),
+                                            defer_loss=defer_loss and args.defer_loss == "on", **pv)
+        latest["image"], latest["radii"] = img, radii
         return loss
+
+    latest = {}
+
+    def step_outputs(loss):
+        """What the step just run handed its caller (--dump-outputs): references, read once the step has finished. The gradients
+        are the ones on the leaves now (a captured step's are rewritten in place by every replay)."""
+        out = {"loss": loss, "image": latest["image"], "radii": latest["radii"]}
+        out.update({"grad_" + k: p.grad for k, p in params.items()})
+        return out
 
     def reduce_grads(loss):
         """Data-parallel fit (--allreduce-grads): sum the gradient block at the rasteriser boundary, ONE collective over the
@@ -464,7 +523,7 @@ def main():
     # The timed steps replay ONE captured step (forward + loss + backward of this rank's views) from a HIP graph: the
     # launch sequence is ~45 small kernels, and enqueueing them one by one leaves the result at the mercy of the host
     # (0.5 ms per step on a quiet box, several ms on a busy one). Collectives stay outside the graph.
-    graph, g_loss, graph_note = None, None, None
+    graph, g_loss, g_out, graph_note = None, None, None, None
     warm_replays = 0
     pipe = []
     if not args.no_graph:
@@ -484,6 +543,7 @@ def main():
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 g_loss = local_step(sync=False)
                 g_loss.backward(seed)
+            g_out = step_outputs(g_loss)
             # warm-up of the replay path itself (graph upload, clocks): untimed. At least --warmup replays, and at least
             # WARM_MS of them: the eager warm-up steps above are host-bound (the GPU idles between their kernels), and the first
             # ~30 ms of back-to-back replays run on a clock that is still ramping (measured: a window of 20 steps behind 5
@@ -508,10 +568,10 @@ def main():
                         with torch.cuda.graph(gph, stream=st, capture_error_mode="thread_local"):
                             gl = local_step(sync=False)
                             gl.backward(seed)
-                    pipe.append((st, gph, gl))
+                    pipe.append((st, gph, gl, step_outputs(gl)))
                 torch.cuda.synchronize()
         except Exception as e:                           # capture is an optimisation of the enqueue path, never a requirement
-            graph, g_loss, graph_note = None, None, f"graph capture failed ({type(e).__name__}: {e}); eager steps"
+            graph, g_loss, g_out, graph_note = None, None, None, f"graph capture failed ({type(e).__name__}: {e}); eager steps"
             R.set_graph_mode(False)
             torch.cuda.synchronize()
 
@@ -533,7 +593,7 @@ def main():
         pending, loss = None, None
         for k in range(args.steps):
             if graph is not None and args.pipeline > 1 and world == 1:
-                st, gph, gl = pipe[k % len(pipe)]
+                st, gph, gl, _ = pipe[k % len(pipe)]
                 with torch.cuda.stream(st):
                     gph.replay()
                 loss = gl
@@ -545,14 +605,22 @@ def main():
             pending.wait()
         t_enq = time.perf_counter() - t0             # host time to enqueue the timed steps (GPU-bound if << dt)
         barrier()
-        return time.perf_counter() - t0, t_enq, loss
+        dt = time.perf_counter() - t0
+        if graph is not None and args.pipeline > 1 and world == 1:
+            out = pipe[(args.steps - 1) % len(pipe)][3]
+        else:
+            out = g_out if graph is not None else step_outputs(loss)
+        return dt, t_enq, loss, dict(out, loss=loss)
 
-    dt, t_enq, loss = timed_window()                 # THE timed region: exactly --steps steps between two barriers
+    dt, t_enq, loss, last_out = timed_window()       # THE timed region: exactly --steps steps between two barriers
+    # the outputs of the last timed step, read before anything else runs on the device
+    dumped = snapshot_outputs(last_out) if args.dump_outputs and rank == 0 else None
+    del last_out
     extra = [timed_window()[0] for _ in range(max(0, args.repeats - 1))]      # repeat statistics (not `value`)
     R.check_overflow()
     # per-step spread (>= 20 timed iterations, median and p10 / p90): every step bracketed by its own HIP events
     step_ms = []
-    if world == 1:
+    if world == 1 and args.full:
         evs = []
         for _ in range(max(20, args.steps)):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -573,7 +641,7 @@ def main():
     # workload, run right after the timed region (events cannot sit inside the captured graph, and the timed steps stay
     # free of the extra event records).
     stage_ms = {}
-    if not args.no_stage_timing:
+    if args.full and not args.no_stage_timing:
         R.enable_stage_timing(True)
         for _ in range(args.steps):
             local_step(sync=False).backward(seed)
@@ -606,14 +674,16 @@ def main():
                        "measured_ms_per_step": dt / args.steps * 1e3}
     if rank == 0:
         # instance count of the published algorithm (every tile of the 3-sigma rects) beside the exactly culled one
-        with torch.no_grad():
-            col = dict(colors_precomp=s.shs.reshape(-1, 3)) if s.use_rgb else dict(shs=s.shs, sh_degree=s.sh_degree)
-            _, _, rctx = R.raster_forward(cams, s.xyz, s.opacity, s.scaling, s.rotation, H=H, W=W, sync=True, split_streams=False,
-                                           **col, **blend, **pv)
-            rect = R.workspace_views(rctx)["rect"].long()
-            D_rect = int((((rect >> 16 & 255) - (rect & 255)) * ((rect >> 24 & 255) - (rect >> 8 & 255))).sum())
-            del rctx
-        D = R.last_num_rendered()
+        D_rect = None
+        if args.full:
+            with torch.no_grad():
+                col = dict(colors_precomp=s.shs.reshape(-1, 3)) if s.use_rgb else dict(shs=s.shs, sh_degree=s.sh_degree)
+                _, _, rctx = R.raster_forward(cams, s.xyz, s.opacity, s.scaling, s.rotation, H=H, W=W, sync=True, split_streams=False,
+                                               **col, **blend, **pv)
+                rect = R.workspace_views(rctx)["rect"].long()
+                D_rect = int((((rect >> 16 & 255) - (rect & 255)) * ((rect >> 24 & 255) - (rect >> 8 & 255))).sum())
+                del rctx
+        D = R.last_num_rendered()          # (plain run: as read back by the first warm-up step, the same workload)
         ab = algorithmic_bytes(P, V, H, W, D, C=12 if s.use_rgb else 192)
         roofline = None
         stages = {}
@@ -672,7 +742,7 @@ def main():
                        else "eager kernel-by-kernel enqueue" + (f" [{graph_note}]" if graph_note else "")},
             "roofline": roofline, "stages": stages,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if not args.pose_batch:
                 # the reference's own 2-call protocol through the drop-in, per view, beside the fused per-view cost —
                 # a HOST-bound figure, taken before the CPU baseline has 16 OpenMP threads spinning beside this one
@@ -682,6 +752,8 @@ def main():
             out["cpu_baseline"] = cpu_baseline(scene_one, args.cpu_seconds, torch_reference=(args.config == "random1k"))
         else:
             out["cpu_baseline"] = None
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         print(json.dumps(out))
     if world > 1:
         tdist.barrier()

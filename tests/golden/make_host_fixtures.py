@@ -19,7 +19,12 @@ import sys
 import types
 
 import numpy as np
-import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import cpu_numerics  # noqa: E402
+
+cpu_numerics.apply(threads=1)      # the CPU arithmetic the tests check these values under (tests/cpu_numerics.py)
+import torch  # noqa: E402
 
 REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_fixtures.npz")

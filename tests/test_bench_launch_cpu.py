@@ -25,8 +25,9 @@ def test_rank_count_mismatch_fails_loudly():
 
 
 def test_self_launch_starts_the_ranks():
+    # the ranks see no GPU, also on a host that has one (an ordinal that does not exist ends the visible-device list)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "1", "--warmup", "0"],
-                       capture_output=True, text=True, cwd=ROOT, env=_env(), timeout=600)
-    assert r.returncode != 0                                                  # no GPU here: every rank refuses to run
+                       capture_output=True, text=True, cwd=ROOT, env=_env(HIP_VISIBLE_DEVICES="-1"), timeout=600)
+    assert r.returncode != 0                                                  # no GPU visible: every rank refuses to run
     assert r.stderr.count("bench.py needs a ROCm device") == 2, r.stderr[-3000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -31,7 +31,7 @@ def _last_json(out: str):
 
 @pytest.mark.timeout(600)
 def test_bench_one_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -46,6 +46,34 @@ def test_bench_one_gpu_line():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
     assert "workload" in d["config"] and "model" not in d["config"]
+    assert d["config"]["repeats"]["windows"] == 5 and d["config"]["step_ms"]["n"] >= 20 and d["config"]["instances_in_3sigma_rects"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes what the last timed
+    step handed its caller: the loss the line reports, the image, the radii and one gradient per leaf, float32."""
+    import numpy as np
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, cwd=ROOT, timeout=560)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "renders/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 8 * 4 / (d["ms_per_step"] * 4e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["stages"] == {} and d["cpu_baseline"] is None
+    c = d["config"]
+    assert c["repeats"]["windows"] == 1 and c["step_ms"] is None and "two_call_ms_per_view" not in c
+    files = sorted(os.listdir(out_dir))
+    names = {"loss", "image", "radii", "grad_xyz", "grad_opacity", "grad_scaling", "grad_rotation", "grad_shs"}
+    assert names <= {f[:-4] for f in files} and all(f.endswith(".npy") for f in files)
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 10**6
+    a = {f[:-4]: np.load(out_dir / f) for f in files}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["image"].shape == (8, 3, 512, 334) and np.isfinite(a["image"]).all()      # (the whole default output fits the budget)
+    assert float(a["loss"]) == c["final_loss"]
+    grad_l1 = sum(float(np.abs(v.astype(np.float64)).sum()) for k, v in a.items() if k.startswith("grad_"))
+    assert grad_l1 == pytest.approx(c["grad_l1"], rel=1e-5)
 
 
 def _run_bench(n_ranks, *extra, backend="gloo"):

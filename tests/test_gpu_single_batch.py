@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import BatchStandIns, batch_inputs, forward_single_view
+from helpers import BatchStandIns, GoldenNpz, batch_inputs, forward_single_view
 
 pytestmark = pytest.mark.gpu
 
@@ -134,7 +134,7 @@ def test_composed_path_with_empty_selections(dev, lo, hi, what):
 # ---- the edit / avatar-drive renderer (renderer_one_shot_edit.py:440-520; VERDICT r5 'next' item 8) ------------------------------------
 @pytest.fixture(scope="module")
 def efx(golden_dir):
-    return np.load(os.path.join(golden_dir, "edit_batch_fixture.npz"), allow_pickle=False)
+    return GoldenNpz(os.path.join(golden_dir, "edit_batch_fixture.npz"))
 
 
 _EDIT_VARIANTS = {"plain": None, "dup": dict(duplication=True, edit_left_only=False), "left": dict(duplication=False, edit_left_only=True)}

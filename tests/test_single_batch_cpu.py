@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import BatchStandIns, batch_inputs
+from helpers import BatchStandIns, GoldenNpz, batch_inputs
 
 
 @pytest.fixture(scope="module")
@@ -92,7 +92,7 @@ def test_forward_single_batch_refuses_cpu_tensors():
 # ---- the edit / avatar-drive renderer (renderer_one_shot_edit.py:440-520) ------------------------------------------------------------
 @pytest.fixture(scope="module")
 def efx(golden_dir):
-    return np.load(os.path.join(golden_dir, "edit_batch_fixture.npz"), allow_pickle=False)
+    return GoldenNpz(os.path.join(golden_dir, "edit_batch_fixture.npz"))
 
 
 def test_edit_colour_weight_rows_equal_the_reference_lookup(efx):

@@ -9,7 +9,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     O=gpurun_out/kstats_$v
     rm -rf $O && mkdir -p $O
     echo "== $v [$ARGS] round $r"
-    timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline $ARGS > $O/bench.json 2> $O/stats.log || { echo FAILED; tail -5 $O/stats.log; continue; }
+    timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline $ARGS > $O/bench.json 2> $O/stats.log || { echo FAILED; tail -5 $O/stats.log; continue; }
     python3 - "$O" "$RX" <<'PY'
 import csv, glob, re, sys
 O, rx = sys.argv[1], sys.argv[2]
@@ -19,7 +19,7 @@ for r in csv.DictReader(open(f)):
         print(f"   {r['Name'][:58]:58s} calls {r['Calls']:>5s} avg_us {float(r['AverageNs'])/1e3:8.2f} min_us {float(r['MinNs'])/1e3:8.2f}")
 PY
     rm -rf $O/stats
-    python3 bench.py --steps 50 --warmup 20 --repeats 3 --no-cpu-baseline $ARGS 2>/dev/null | python3 -c "
+    python3 bench.py --steps 50 --warmup 20 --repeats 3 --full --no-cpu-baseline $ARGS 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); c=d['config']
 print('   bench', round(d['value']), 'renders/s', round(d['ms_per_step'],4), 'ms; windows median', round(c['repeats']['ms_per_step_median'],4), {k: round(v['ms'],4) for k,v in d.get('stages',{}).items()})"

@@ -5,6 +5,6 @@ mkdir -p gpurun_out
 for rep in 1 2; do
 for f in tools/abl/*.so; do
   v=$(basename $f .so)
-  GH_RASTER_LIB=$GRAFT_REPO_ROOT/$f timeout 200 python bench.py --no-cpu-baseline --steps 30 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value']), {k: round(v['ms'],4) for k,v in d['stages'].items()})" | tee -a gpurun_out/abl.log
+  GH_RASTER_LIB=$PWD/$f timeout 200 python bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value']), {k: round(v['ms'],4) for k,v in d['stages'].items()})" | tee -a tools/abl/abl.log
 done
 done

@@ -32,7 +32,7 @@ def suffix(w):
 
 def kernel_stats(w, desc, args):
     rows = list(csv.DictReader(open(f"{O}/{w}/kernel_stats.csv")))
-    out = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py {args} --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline  (MI355X, "
+    out = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py {args} --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline  (MI355X, "
            f"{desc}; tools/refresh_profiles.sh; source {src})", "name,calls,total_ns,avg_ns,pct,min_ns,max_ns"]
     for r in rows[:36]:
         n = re.sub(r"\(.*", "", r["Name"])[:70]
@@ -53,7 +53,7 @@ def sq(w, desc, args):
                 lines.append(l.strip())
                 # several instantiations of a template share the name: keep the one with the larger value (the dominant one)
                 vals[(k, c)] = max(vals.get((k, c), 0.0), float(v))
-    hdr = (f"# rocprofv3 --kernel-trace --pmc <4 counters per pass> -- python3 bench.py {args} --steps 4 --warmup 2 --repeats 1 --no-cpu-baseline "
+    hdr = (f"# rocprofv3 --kernel-trace --pmc <4 counters per pass> -- python3 bench.py {args} --steps 4 --warmup 2 --repeats 1 --full --no-cpu-baseline "
            f"--no-stage-timing ; per-dispatch averages ({desc}; tools/refresh_profiles.sh, tools/summarize_pmc.py; source {src})\n"
            "kernel,counter,dispatches,avg_value\n")
     open(f"profiles/{tag}_pmc_sq_kernels{suffix(w)}.csv", "w").write(hdr + "\n".join(sorted(set(lines))) + "\n")

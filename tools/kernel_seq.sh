@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 K=$1; shift
 O=gpurun_out/kseq
 rm -rf $O && mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace -d $O/tr -o tr --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $O/bench.json 2> $O/log.txt || exit 1
+timeout 300 rocprofv3 --kernel-trace -d $O/tr -o tr --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline "$@" > $O/bench.json 2> $O/log.txt || exit 1
 python3 - "$K" <<'PY'
 import csv, glob, sys
 f = glob.glob("gpurun_out/kseq/tr/**/*kernel_trace.csv", recursive=True)[0]

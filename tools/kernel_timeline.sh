@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/ktl
 rm -rf $O && mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace -d $O/tr -o tr --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-stage-timing "$@" > $O/bench.json 2> $O/log.txt || exit 1
+timeout 300 rocprofv3 --kernel-trace -d $O/tr -o tr --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline --no-stage-timing "$@" > $O/bench.json 2> $O/log.txt || exit 1
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/ktl/tr/**/*kernel_trace.csv", recursive=True)[0]

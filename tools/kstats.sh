@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/kstats
 rm -rf $O && mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $O/bench.json 2> $O/stats.log || exit 1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline "$@" > $O/bench.json 2> $O/stats.log || exit 1
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/kstats/stats/**/*kernel_stats.csv", recursive=True)[0]

@@ -19,7 +19,7 @@ def per_kernel(path, counter):
 
 fe, wr = per_kernel(fetch_csv, "FETCH_SIZE"), per_kernel(write_csv, "WRITE_SIZE")
 note = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py <workload args> --steps 3 "
-        "--warmup 2 --no-cpu-baseline --no-stage-timing`; KB per dispatch; traffic_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per "
+        "--warmup 2 --full --no-cpu-baseline --no-stage-timing`; KB per dispatch; traffic_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per "
         "MI355X_MICROARCH.md (gfx950 FETCH_SIZE counts wide streaming reads at half)")
 kern = {}
 for k in sorted(set(fe) | set(wr), key=lambda k: -(2 * fe.get(k, 0) + wr.get(k, 0))):
