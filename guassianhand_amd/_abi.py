@@ -15,8 +15,13 @@ GH_FLAG_DEFER_LOSS_SUM = 64
 GH_FLAG_FRESH_ORDER = 128
 GH_VERSION_MAJOR, GH_VERSION_MINOR = 0, 8        # the header this mirror was written against (checked against gh_version() on load)
 GH_ABI_TAG = 0x47480000 | (GH_VERSION_MAJOR << 8) | GH_VERSION_MINOR
-GH_COUNTER_ERROR_MASK = 15     # GhCounters.overflow bits 0-3: errors
-GH_COUNTER_DEPTH24_OK = 16     # bit 4: information (the depth keys' top byte did not vary)
+# GhCounters.overflow: bits 0-3 are errors, bit 4 is information (the depth keys' top byte did not vary)
+GH_COUNTER_OVERFLOW = 1
+GH_COUNTER_STALE_LISTS = 2
+GH_COUNTER_BOUND_MISS = 4
+GH_COUNTER_DEPTH24_FAILED = 8
+GH_COUNTER_ERROR_MASK = GH_COUNTER_OVERFLOW | GH_COUNTER_STALE_LISTS | GH_COUNTER_BOUND_MISS | GH_COUNTER_DEPTH24_FAILED
+GH_COUNTER_DEPTH24_OK = 16
 
 GH_OK = 0
 GH_ERR_INVALID_ARG = -1

@@ -79,7 +79,7 @@ __device__ __forceinline__ void gh_store_varying_bits(uint2* __restrict__ key_bi
     // when it does and this sort has no pass for it (nbits24), the call is invalid (one thread per call: no contention)
     if (wide_flag) {
       if ((varying >> 24) == 0u) atomicOr(wide_flag, GH_COUNTER_DEPTH24_OK);
-      else if (nbits24) atomicOr(wide_flag, 8u);
+      else if (nbits24) atomicOr(wide_flag, GH_COUNTER_DEPTH24_FAILED);
     }
   }
   __syncthreads();
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(GH_BLOCK) void gh_emit_kernel(
     ctr->num_rendered = total;
     if (view_start) view_start[n_views] = total;
     // (the projection kernel cleared the word; bits 3 / 4 may already be set; a BINNING-only re-run clears a stale bit 0)
-    if (total > cap) atomicOr(&ctr->overflow, 1u); else atomicAnd(&ctr->overflow, ~1u);
+    if (total > cap) atomicOr(&ctr->overflow, GH_COUNTER_OVERFLOW); else atomicAnd(&ctr->overflow, ~GH_COUNTER_OVERFLOW);
   }
   const uint32_t wave_base = blk_off + woff;
   // first emit slot of every view = that of the first Gaussian of its segment of the depth order (position v * P)

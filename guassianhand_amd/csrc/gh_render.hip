@@ -576,7 +576,7 @@ __global__ __launch_bounds__(GH_BLOCK) void gh_render_fwd_kernel(
   const bool wave_miss = !__all(p.done != 0);       // some in-image pixel of this block never reached the stop
   // what the NEXT call may rely on: every pixel of the block passed the stricter virtual threshold inside this list
   const bool wave_unsat = SEEN ? !__all(p.vdone != 0) : wave_miss;
-  if (bounded && wave_miss && lane == 0) atomicOr(&ctr->overflow, 4u);
+  if (bounded && wave_miss && lane == 0) atomicOr(&ctr->overflow, GH_COUNTER_BOUND_MISS);
   if (SEEN && total == 0 && tid == 0 && quad == 0) {   // empty list: no bound, no block of it stops anything
     tile_depth_seen[2 * tile] = __uint_as_float(0x7F800000u); tile_depth_seen[2 * tile + 1] = __uint_as_float(0u);
   }
@@ -778,7 +778,7 @@ void gh_launch_render_fwd(const GhDims* d, const GhGrid& g, const GhInputs* in, 
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, ranges, order, r0, r1, r2, in->cams, g.H, g.W, g.gx,
                        g.tiles, image, alpha, fT, nc, tw, ck, fC, items, ctr, (const uint32_t*)(ws + L.render_guard),
-                       wg == ws ? 11u : GH_COUNTER_ERROR_MASK, bound, seen, seen_scale, seen_slack, gid, geom, l1,
+                       wg == ws ? GH_COUNTER_ERROR_MASK & ~GH_COUNTER_BOUND_MISS : GH_COUNTER_ERROR_MASK, bound, seen, seen_scale, seen_slack, gid, geom, l1,
                        n_tiles_call, fine_k, fine_min, (uint32_t)g.n_items, (uint32_t*)(ws + L.render_guard) + 1,
                        g.total_tiles <= GH_ORDER_TILES ? tw + 3 * (size_t)n_tiles_call : nullptr, gh_fwd_fine_launch(g) ? 1u : 0u, gh_bwd_class_mode(g));
   };
@@ -1378,7 +1378,7 @@ __global__ __launch_bounds__(GH_BLOCK) void gh_refresh_attr_kernel(GhInputs in, 
   if (in.colors_precomp) gh_blended_rgb(in, flags, row, rgb);
   else { const float4 c4 = sh_rgb[t]; rgb[0] = c4.x; rgb[1] = c4.y; rgb[2] = c4.z; }
   attr[t] = make_float4(op, rgb[0], rgb[1], rgb[2]);
-  if (op > cull_bound[t]) atomicOr(&ctr->overflow, 2u);
+  if (op > cull_bound[t]) atomicOr(&ctr->overflow, GH_COUNTER_STALE_LISTS);
 }
 
 __global__ __launch_bounds__(GH_BLOCK) void gh_refresh_instance_kernel(uint32_t cap, int gx, int tiles, float rtiles, float rgx,

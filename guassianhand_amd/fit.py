@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _abi
 from . import dist as ghdist
 from .renderer import GaussianModel
 from .uvmap import (ActiveTexels, AdamReg, adam_group_step, reg_total, to_reference_layout, uv_gather, uv_gather2,
@@ -296,7 +297,7 @@ class OneShotFit(nn.Module):
         ovf = None
         if world > 1 and self.color_w.is_cuda:
             ovf = torch.zeros((), device=self.color_w.device) if local_guard is None else \
-                (local_guard.view(torch.int32)[1] & 15).ne(0).float()      # the error bits (GH_COUNTER_ERROR_MASK); bit 4 is information
+                (local_guard.view(torch.int32)[1] & _abi.GH_COUNTER_ERROR_MASK).ne(0).float()      # bit 4 is information
         blk = None
         if use_block:
             from . import rasterizer as R
@@ -442,10 +443,10 @@ class CapturedFitStep:
         """Host read-back of the captured render's counters: raises rasterizer.GhOverflowError if a replay overflowed."""
         from . import rasterizer as R
         for counters, cap, key, full in self.counters:
-            c4 = counters.tolist()
+            w = R.counter_word(counters.tolist())
             # stale static lists (an opacity above their bound) / GH_FLAG_DEPTH24 not holding / an instance overflow: the rasteriser
             # learns what the word says (capacity, verdicts, caches cleared) and raises the matching error
-            R.report_counter_word(key, c4[1], c4[0] & 0xFFFFFFFF, cap, c4[2] & 0xFFFFFFFF, dev=counters.device,
-                                  where=(" [inside the captured fit step: the next replay() rebuilds and re-captures]" if (c4[1] & 2) else
-                                         " [inside the captured fit step: construct a new CapturedFitStep]" if (c4[1] & 8) else
-                                         " inside the captured fit step"), learn24=full)
+            where = (" [inside the captured fit step: the next replay() rebuilds and re-captures]" if w.stale else
+                     " [inside the captured fit step: construct a new CapturedFitStep]" if w.depth24_failed else
+                     " inside the captured fit step")
+            R.report_counter_word(key, w.bits, w.d, cap, w.reserved0, dev=counters.device, where=where, learn24=full)

@@ -218,23 +218,54 @@ def _state(dev=None) -> _DeviceState:
     return st
 
 
+class CounterWord(NamedTuple):
+    """A forward's GhCounters as read back, decoded once (counter_word): what each path then does with it is its own policy."""
+    d: int             # tile instances D
+    bits: int          # GhCounters.overflow: error bits 0-3, information bit 4
+    reserved0: int     # after a split call: the max_instances that would have given each half a large enough share (need())
+
+    errors = property(lambda w: w.bits & _abi.GH_COUNTER_ERROR_MASK)
+    overflow = property(lambda w: bool(w.bits & _abi.GH_COUNTER_OVERFLOW))            # D > max_instances (split: a half's share)
+    stale = property(lambda w: bool(w.bits & _abi.GH_COUNTER_STALE_LISTS))            # a refresh met an opacity above its lists' bound
+    bound_miss = property(lambda w: bool(w.bits & _abi.GH_COUNTER_BOUND_MISS))        # a pixel ran off a list the occlusion bound cut
+    depth24_failed = property(lambda w: bool(w.bits & _abi.GH_COUNTER_DEPTH24_FAILED))
+    depth24_ok = property(lambda w: bool(w.bits & _abi.GH_COUNTER_DEPTH24_OK))        # the depth keys' top byte did not vary
+
+    def need(self, split: bool) -> int:       # the instance count that sizes the shape's next capacity
+        return max(self.d, self.reserved0) if split else self.d
+
+
+def counter_word(c4) -> CounterWord:           # c4: the host read-back of a GhCounters' int32 view
+    return CounterWord(c4[0] & 0xFFFFFFFF, c4[1] & 0xFFFFFFFF, c4[2] & 0xFFFFFFFF)
+
+
 def _learn_depth24(st: _DeviceState, key, flags_word: int, d: int = 1) -> None:
     """Update the GH_FLAG_DEPTH24 verdict of a call shape from a counter word that has been read back — the word of a FULL forward
     whose depth sort ran (callers pass nothing else: a refresh, a shared call or a call with nothing to project sorted nothing, and
     a word that says nothing must not decide anything). d: the call's instance count; with d = 0 no key took part in
     the (OR, AND) of the key bits, so "the top byte did not vary" is vacuous and "bit 4 absent" impossible: unknown stays unknown."""
-    if flags_word & 8:
+    w = CounterWord(d, flags_word, 0)
+    if w.depth24_failed:
         st.depth24[key] = False
-    elif d == 0:
+    elif w.d == 0:
         return
-    elif flags_word & _abi.GH_COUNTER_DEPTH24_OK:
+    elif w.depth24_ok:
         st.depth24.setdefault(key, True)
-    elif not (flags_word & 1):             # a complete call whose depths' top byte varies (truncated lists prove nothing)
+    elif not w.overflow:                   # a complete call whose depths' top byte varies (truncated lists prove nothing)
         st.depth24[key] = False
+
+
+def _grow_capacity(st: _DeviceState, key, need: int, floor: int = 0) -> None:
+    """Raise the learned capacity of a call shape to hold `need` instances with room to spare (it never shrinks)."""
+    st.capacity[key] = max(st.capacity.get(key, 0), int(need * 1.5) + 1024, floor)
 
 
 _DEPTH24_MSG = ("the visible depths span more than the 24 key bits the three-pass depth sort covers; the call returned a NaN image; "
                 "the four-pass sort is used for this call shape from now on, re-run the step")
+_STALE_MSG = ("an opacity rose above the bound the static tile lists were built for; the call returned a NaN image; "
+              "the geometry caches are cleared, re-run the step (it rebuilds the lists)")
+_MISS_MSG = ("a pixel ran off the end of a tile list truncated by the speculative occlusion bound (the Gaussians moved further than "
+             "the margin); that pixel is NaN; the bound has been dropped, re-run the step")
 _PENDING_MAX = 64
 
 
@@ -244,67 +275,55 @@ class _Pending:
     __slots__ = ("st", "ev", "host", "cap", "key", "done", "d", "over", "stale", "miss", "wide", "dbound", "told", "learn24")
 
     def __init__(self, st, ev, host, cap, key, dbound=None, learn24=True):
-        self.st, self.ev, self.host, self.cap, self.key, self.done, self.d, self.over, self.stale = st, ev, host, cap, key, False, 0, False, False
-        self.miss, self.wide, self.dbound = False, False, dbound
+        self.st, self.ev, self.host, self.cap, self.key, self.dbound = st, ev, host, cap, key, dbound
+        # the verdict, once resolved: D, any error bit, stale lists, a bound miss, GH_FLAG_DEPTH24 failed (CounterWord)
+        self.done, self.d, self.over, self.stale, self.miss, self.wide = False, 0, False, False, False, False
         self.learn24 = learn24     # a full forward (the depth sort ran): its counter word says whether GH_FLAG_DEPTH24 holds
         self.told = False          # the caller has been given this record's error (a look at the counters by the geometry-reuse check is not that)
 
     def resolve(self) -> bool:
-        """True when the call overflowed its capacity (the learned capacity of its shape is raised then)."""
+        """True when the call's counters hold an error bit (what the word says has been learned then)."""
         st = self.st
         with st.lock:
             if not self.done:
                 self.ev.synchronize()
-                c = self.host.tolist()
-                self.d = c[0] & 0xFFFFFFFF
-                st.last_D = self.d
-                # overflowed = the device-side error bits, nothing else; a split call's reserved[0] (the max_instances that would
-                # give each half a large enough share) only sizes the NEXT capacity
-                self.over = (c[1] & _abi.GH_COUNTER_ERROR_MASK) != 0
-                self.stale = (c[1] & 2) != 0
-                self.miss = (c[1] & 4) != 0
-                self.wide = (c[1] & 8) != 0                    # GH_FLAG_DEPTH24 did not hold: four passes for this shape from now on
+                w = counter_word(self.host.tolist())
+                st.last_D = w.d
                 if self.learn24:
-                    _learn_depth24(st, self.key, c[1], self.d)
-                if self.miss and self.dbound is not None:      # the speculation failed: the re-run of the step renders without a bound
+                    _learn_depth24(st, self.key, w.bits, w.d)
+                if w.bound_miss and self.dbound is not None:   # the speculation failed: the re-run of the step renders without a bound
                     self.dbound.clear()
                     self.dbound.misses += 1
                 self.dbound = None
-                need = (c[2] & 0xFFFFFFFF) if self.key[-1] else self.d
-                if self.over and (c[1] & 3):           # stale lists, or lists truncated by an instance overflow: never re-use them
+                if w.overflow or w.stale:                      # stale lists, or lists truncated by an instance overflow: never re-use them
                     GeometryCache.clear_all()
-                if self.over and (c[1] & 1):
-                    st.capacity[self.key] = max(st.capacity.get(self.key, 0), int(max(need, self.d) * 1.5) + 1024)
+                if w.overflow:                                 # (a split call's reserved[0] sizes the next capacity)
+                    _grow_capacity(st, self.key, w.need(self.key[-1]))
                 st.free_slots.append((self.host, self.ev))
                 self.host = self.ev = None
+                self.d, self.over, self.stale, self.miss, self.wide = w.d, w.errors != 0, w.stale, w.bound_miss, w.depth24_failed
                 self.done = True
         return self.over
 
-    def message(self) -> str:
+    def kind(self):
+        """(rank, exception class, message) of a bad record. Of several, check_overflow() raises the highest rank first: stale lists
+        and a capacity overflow ask for a rebuild or a larger workspace, a depth-key verdict or a bound miss only for the step again."""
+        capacity = (f"tile instances D={self.d} exceeded max_instances={self.cap}; the call returned a NaN image; "
+                    "capacity raised, re-run the step")
         if self.stale:
-            return _STALE_MSG
-        if self.miss and not (self.over and self.d > self.cap):
-            return _MISS_MSG
-        if not self.d > self.cap and self.wide and not self.stale and not self.miss:
-            return _DEPTH24_MSG
-        return (f"tile instances D={self.d} exceeded max_instances={self.cap}; the call returned a NaN image; "
-                "capacity raised, re-run the step")
+            return 3, GhStaleGeometryError, _STALE_MSG
+        if self.d > self.cap:
+            return 2, GhOverflowError, capacity
+        if self.miss:
+            return 0, GhDepthBoundMiss, _MISS_MSG
+        if self.wide:
+            return 1, GhOverflowError, _DEPTH24_MSG
+        return 0, GhOverflowError, capacity           # bit 0 alone with D <= max_instances: a split call's half outgrew its share
 
     def error(self) -> GhOverflowError:
         self.told = True
-        if self.stale:
-            return GhStaleGeometryError(self.message())
-        if self.miss and not self.d > self.cap:
-            return GhDepthBoundMiss(self.message())
-        return GhOverflowError(self.message())
-
-
-_STALE_MSG = ("an opacity rose above the bound the static tile lists were built for; the call returned a NaN image; "
-              "the geometry caches are cleared, re-run the step (it rebuilds the lists)")
-
-
-_MISS_MSG = ("a pixel ran off the end of a tile list truncated by the speculative occlusion bound (the Gaussians moved further than "
-             "the margin); that pixel is NaN; the bound has been dropped, re-run the step")
+        _, exc, msg = self.kind()
+        return exc(msg)
 
 
 def last_guard(dev=None):
@@ -401,22 +420,21 @@ def report_counter_word(key, flags_word: int, d: int, cap: int, reserved0: int =
     """Act on a GhCounters.overflow word read back from a workspace the caller holds itself (a captured graph's, see
     fit.CapturedFitStep.check): learn what it says (capacity, GH_FLAG_DEPTH24 verdict, stale caches) and raise the matching error.
     learn24: the word is a FULL forward's (its depth sort ran); a refresh over static lists passes False."""
+    w = CounterWord(d, flags_word, reserved0)
     st = _state(dev)
     with st.lock:
-        st.last_D = d
-        if learn24 or (flags_word & 8):
-            _learn_depth24(st, key, flags_word, d)
-        if flags_word & 2:                                  # a static-geometry replay met an opacity above its lists' bound
-            GeometryCache.clear_all()
+        st.last_D = w.d
+        if learn24 or w.depth24_failed:
+            _learn_depth24(st, key, w.bits, w.d)
+        if not w.errors:
+            return
+        GeometryCache.clear_all()                           # stale lists, or lists truncated by an overflow: never refreshed again
+        if w.stale:                                         # a static-geometry replay met an opacity above its lists' bound
             raise GhStaleGeometryError(_STALE_MSG + where)
-        if flags_word & 8:                                  # GH_FLAG_DEPTH24 did not hold for a captured call
-            GeometryCache.clear_all()
+        if w.depth24_failed:                                # GH_FLAG_DEPTH24 did not hold for a captured call
             raise GhOverflowError(_DEPTH24_MSG + where)
-        if flags_word & _abi.GH_COUNTER_ERROR_MASK:         # the device-side flag decides; reserved[0] of a split call sizes the next capacity
-            need = max(d, reserved0 if key[-1] else d)
-            st.capacity[key] = max(st.capacity.get(key, 0), int(need * 1.5) + 1024)
-            GeometryCache.clear_all()                       # lists truncated by the overflow must not be refreshed again
-            raise GhOverflowError(f"tile instances D={d} exceeded max_instances={cap}" + (where or " inside a captured graph"))
+        _grow_capacity(st, key, w.need(key[-1]))            # any other error bit: a larger capacity (reserved[0] sizes a split call's)
+        raise GhOverflowError(f"tile instances D={w.d} exceeded max_instances={cap}" + (where or " inside a captured graph"))
 
 
 def check_overflow(block: bool = True, keep_recent: int = 0, dev=None) -> None:
@@ -426,9 +444,9 @@ def check_overflow(block: bool = True, keep_recent: int = 0, dev=None) -> None:
     st = _state(dev)
     with st.lock:
         for counters, cap, key, full in list(st.graph_counters.values()):   # graph mode: workspaces are static, read them directly
-            c4 = counters.tolist()
-            report_counter_word(key, c4[1], c4[0] & 0xFFFFFFFF, cap, c4[2] & 0xFFFFFFFF, dev=st.index,
-                                where=" [inside a captured graph: capture again]" if (c4[1] & 10) else "", learn24=full)
+            w = counter_word(counters.tolist())
+            report_counter_word(key, w.bits, w.d, cap, w.reserved0, dev=st.index,
+                                where=" [inside a captured graph: capture again]" if (w.stale or w.depth24_failed) else "", learn24=full)
         keep, bad = [], []
         n_old = len(st.pending) - keep_recent if keep_recent > 0 else 0
         for i, pc in enumerate(st.pending):
@@ -442,11 +460,9 @@ def check_overflow(block: bool = True, keep_recent: int = 0, dev=None) -> None:
             if pc.resolve():
                 bad.append(pc)
         if bad:
-            # ONE error per call, the most severe first: stale lists / a capacity overflow ask for a rebuild or a larger
-            # workspace, an occlusion-bound miss or a depth-key verdict only for the step again; the records not reported now stay
-            # in the list (done, untold) and surface at the next check instead of being dropped.
-            sev = lambda p: 3 if p.stale else (2 if (p.over and p.d > p.cap) else (1 if p.wide and not p.miss else 0))
-            worst = max(bad, key=sev)
+            # ONE error per call, the highest-ranked first (_Pending.kind); the records not reported now stay in the
+            # list (resolved, untold) and surface at the next check instead of being dropped.
+            worst = max(bad, key=lambda p: p.kind()[0])
             st.pending = [p for p in bad if p is not worst] + keep
             raise worst.error()
         st.pending = keep
@@ -711,13 +727,12 @@ def _forward_refresh(st, L, dev, c: _Call, g0: _Ctx, return_alpha: bool, sync, e
     if sync is None:
         sync = not expect_backward
     if sync:
-        c4 = counters.tolist()
-        st.last_D = c4[0] & 0xFFFFFFFF
-        if c4[1] & 2:
+        w = counter_word(counters.tolist())
+        st.last_D = w.d
+        if w.stale or w.overflow:                   # (no depth sort in a refresh: nothing to learn about GH_FLAG_DEPTH24)
             GeometryCache.clear_all()
-            raise GhStaleGeometryError(_STALE_MSG)
-        if c4[1] & 1:
-            GeometryCache.clear_all()
+            if w.stale:
+                raise GhStaleGeometryError(_STALE_MSG)
             raise GhOverflowError("the static tile lists were built by a call that overflowed its capacity; caches cleared")
     elif _policy.graph_mode:
         st.graph_counters[ws.data_ptr()] = (counters, cap, gkey, False)       # (a refresh: no depth sort ran, nothing to learn about it)
@@ -801,29 +816,26 @@ def _forward_full(st, L, dev, c: _Call, return_alpha: bool, sync, expect_backwar
             if not do_sync:
                 check_overflow(block=False, keep_recent=2, dev=st.index)  # an overflow of an earlier sync-free call surfaces at most two calls late
         if do_sync:
-            c4 = counters.tolist()                        # the one host read-back, as in the reference wrapper
-            d = c4[0] & 0xFFFFFFFF
-            st.last_D = d
-            _learn_depth24(st, key, c4[1], d)
-            if c4[1] & 8:                                      # the three-pass depth sort does not cover this call's depths
+            w = counter_word(counters.tolist())               # the one host read-back, as in the reference wrapper
+            st.last_D = w.d
+            _learn_depth24(st, key, w.bits, w.d)
+            if w.depth24_failed:                               # the three-pass depth sort does not cover this call's depths
                 if depth_bound is not None:
                     depth_bound.clear()
                 continue
-            over = (c4[1] & 1) != 0
-            need = max(d, c4[2] & 0xFFFFFFFF) if c.split else d   # split: the capacity that gives each half a large enough share
-            if over:
+            if w.overflow:
                 if max_instances is not None:
-                    raise GhOverflowError(f"tile instances D={d} exceed max_instances={cap}")
-                st.capacity[key] = int(need * 1.5) + 1024
+                    raise GhOverflowError(f"tile instances D={w.d} exceed max_instances={cap}")
+                _grow_capacity(st, key, w.need(c.split))       # (above `cap`, the capacity it overflowed)
                 if depth_bound is not None:
                     depth_bound.clear()                        # (the truncated lists' report is not a bound)
                 continue                                       # (the too-small workspace is simply dropped)
-            if c4[1] & 4:                                      # the occlusion bound missed: the same call again, unbounded
+            if w.bound_miss:                                   # the occlusion bound missed: the same call again, unbounded
                 depth_bound.clear()
                 depth_bound.misses += 1
                 continue
             if max_instances is None and key not in st.capacity:
-                st.capacity[key] = max(int(need * 1.5) + 1024, 1 << 16)
+                _grow_capacity(st, key, w.need(c.split), floor=1 << 16)
         elif _policy.graph_mode:
             # every captured workspace is registered (keyed by its address, so a workspace re-used by later captures is
             # listed once); check_overflow() reads each of them

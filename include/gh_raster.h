@@ -222,8 +222,12 @@ typedef struct GhCounters {
   uint32_t reserved[2];  /* [0] after a GH_FLAG_SPLIT_STREAMS forward: the max_instances that would have sufficed */
 } GhCounters;
 
-#define GH_COUNTER_ERROR_MASK 15u
-#define GH_COUNTER_DEPTH24_OK 16u
+#define GH_COUNTER_OVERFLOW 1u          /* bit 0 */
+#define GH_COUNTER_STALE_LISTS 2u       /* bit 1 */
+#define GH_COUNTER_BOUND_MISS 4u        /* bit 2 */
+#define GH_COUNTER_DEPTH24_FAILED 8u    /* bit 3 */
+#define GH_COUNTER_ERROR_MASK (GH_COUNTER_OVERFLOW | GH_COUNTER_STALE_LISTS | GH_COUNTER_BOUND_MISS | GH_COUNTER_DEPTH24_FAILED)
+#define GH_COUNTER_DEPTH24_OK 16u       /* bit 4 */
 
 /* Upstream gradient + outputs of gh_backward. Any output pointer may be NULL (that gradient is skipped). */
 typedef struct GhGrads {

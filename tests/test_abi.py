@@ -229,7 +229,7 @@ def test_product_never_imports_oracle():
 
 
 def test_python_mirror_follows_the_header_field_by_field():
-    """GhLayout's field order and the GH_FLAG_* values of the ctypes mirror are read off include/gh_raster.h."""
+    """GhLayout's field order and the GH_FLAG_* / GH_COUNTER_* values of the ctypes mirror are read off include/gh_raster.h."""
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -244,6 +244,13 @@ def test_python_mirror_follows_the_header_field_by_field():
     for name, val in flags.items():
         if name != "GH_FLAG_NONE":
             assert getattr(_abi, name) == int(val), name
+    bits = dict(re.findall(r"#define (GH_COUNTER_[A-Z0-9_]+) (\d+)u", h))
+    assert set(bits) == {"GH_COUNTER_OVERFLOW", "GH_COUNTER_STALE_LISTS", "GH_COUNTER_BOUND_MISS", "GH_COUNTER_DEPTH24_FAILED",
+                         "GH_COUNTER_DEPTH24_OK"}
+    for name, val in bits.items():
+        assert getattr(_abi, name) == int(val), name
+    mask = re.search(r"#define GH_COUNTER_ERROR_MASK \(([A-Z0-9_ |]+)\)", h).group(1).split("|")
+    assert _abi.GH_COUNTER_ERROR_MASK == sum(getattr(_abi, n.strip()) for n in mask) == 15
 
 
 def test_workspace_layout_properties_over_random_dims(gh_lib_path):
