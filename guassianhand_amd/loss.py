@@ -104,44 +104,32 @@ def fit_image_loss(image, alpha, gt_rgb, gt_mask, bbox_mask=None, lambda_l1: flo
 
 # ---------------------------------------------------------------------------------------------------
 class _RenderedLoss(torch.autograd.Function):
-    """Render + image loss as ONE autograd node. The loss kernel leaves dL/dimage (and dL/dalpha) unscaled; the upstream
-    dL/dloss reaches the render backward as a device scalar (GhGrads.upstream_scale) and is applied while the kernel reads
-    its pixels, so the autograd product `dL/dimage * dL/dloss` costs no pass over the images."""
+    """Render + image loss as ONE autograd node (the render and the gradient routing are rasterize_views', rasterizer._views_*).
+    The loss kernel leaves dL/dimage (and dL/dalpha) unscaled; the upstream dL/dloss reaches the render backward as a device scalar
+    (GhGrads.upstream_scale) and is applied while the kernel reads its pixels, so the autograd product `dL/dimage * dL/dloss`
+    costs no pass over the images."""
 
     @staticmethod
-    def forward(ctx, spec, cache, cams, H, W, sh_degree, scale_modifier, use_rgb, sync, max_instances, per_view, defer_loss, xyz, opacity,
-                scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b):
+    def forward(ctx, a, cams, *gaussians):
         from . import rasterizer as R
-        kind = spec[0]
-        kw = dict(colors_precomp=shs.reshape(shs.shape[0], 3)) if use_rgb else dict(shs=shs)
-        if kind == "l1":                             # the fused epilogue reads the target as it lies: float32, contiguous, image-shaped
+        spec = a.spec
+        if spec[0] == "l1":                          # the fused epilogue reads the target as it lies: float32, contiguous, image-shaped
             tgt = spec[1].detach().float().contiguous()
-            if tuple(tgt.shape) != (cams.reshape(-1, 40).shape[0], 3, H, W):
+            if tuple(tgt.shape) != (cams.reshape(-1, 40).shape[0], 3, a.H, a.W):
                 raise ValueError("image and target must have the same shape")
-            spec = ("l1", tgt)
-        elif kind == "fit":
-            f32 = lambda t: None if t is None else t.detach().float().contiguous()
-            spec = ("fit", f32(spec[1]), f32(spec[2]), f32(spec[3])) + tuple(spec[4:])
-        image, radii, rctx = R.cached_raster_forward(cache, cams, xyz, opacity, scaling, rotation, H=H, W=W, sh_degree=sh_degree,
-                                                     scale_modifier=scale_modifier, xyz_b=xyz_b, opacity_b=opacity_b,
-                                                     color_w=color_w, color_b=color_b, sync=sync, max_instances=max_instances,
-                                                     return_alpha=(kind == "fit"), per_view_gaussians=per_view,
-                                                     l1_target=spec[1] if kind == "l1" else None,
-                                                     fit_loss=spec[1:] if kind == "fit" else None, defer_loss=defer_loss, **kw)
-        guard = rctx.ws[:16]                          # device-side overflow guard: an overflowed render yields loss NaN, zero gradients
-        if kind == "l1":
-            # the render kernel's epilogue has produced both (GhOutputs.l1_*) wherever the library fuses them; else one pass over the image
-            loss, dimg = rctx.l1 if rctx.l1 is not None else _l1_kernel(image, spec[1], guard)
+            image, radii, rctx = R._views_forward(ctx, a, cams, gaussians, l1_target=tgt)
+            # the render kernel's epilogue has produced both (GhOutputs.l1_*) wherever the library fuses them; else one pass over the
+            # image, with the forward's counters as the device-side overflow guard (an overflowed render: loss NaN, zero gradients)
+            loss, dimg = rctx.l1 if rctx.l1 is not None else _l1_kernel(image, tgt, rctx.ws[:16])
             dal = None
-        elif kind == "fit":
-            loss, dimg, dal = rctx.fit if rctx.fit is not None else _fit_kernel(image, rctx.alpha, *spec[1:], guard=guard)
+        elif spec[0] == "fit":
+            f32 = lambda t: None if t is None else t.detach().float().contiguous()
+            fit = (f32(spec[1]), f32(spec[2]), f32(spec[3])) + tuple(spec[4:])
+            image, radii, rctx = R._views_forward(ctx, a, cams, gaussians, fit_loss=fit)
+            loss, dimg, dal = rctx.fit if rctx.fit is not None else _fit_kernel(image, rctx.alpha, *fit, guard=rctx.ws[:16])
         else:
-            raise ValueError(kind)
-        ctx.rctx, ctx.dimg, ctx.dal, ctx.use_rgb = rctx, dimg, dal, use_rgb
-        # (the backward kernels re-read the inputs through the context's pointers: autograd's version check, as in rasterizer.py)
-        ctx.save_for_backward(*[t for t in (cams, xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b) if t is not None])
-        ctx.set_materialize_grads(False)             # no image-sized zero tensors for the outputs that carry no gradient
-        ctx.shapes = [None if t is None else t.shape for t in (xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b)]
+            raise ValueError(spec[0])
+        ctx.dimg, ctx.dal = dimg, dal
         alpha = rctx.alpha if rctx.alpha is not None else image.new_zeros(0)
         ctx.mark_non_differentiable(image, alpha, radii)
         return loss, image, alpha, radii
@@ -149,28 +137,13 @@ class _RenderedLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _gi, _ga, _gr):
         from . import rasterizer as R
-        ctx.saved_tensors
-        g = R.raster_backward(ctx.rctx, ctx.dimg, want_means2D=False, dL_dalpha=ctx.dal, grad_scale=g_loss,
-                              want=R._wanted(ctx.needs_input_grad[12:21], ctx.use_rgb))
-        ctx.rctx = None
-        s = ctx.shapes
-        col = g.get("colors_precomp" if ctx.use_rgb else "shs")
-        opt = lambda k, i: g[k].reshape(s[i]) if (s[i] is not None and k in g) else None
-        return (None,) * 12 + (opt("means3D", 0), opt("opacities", 1), opt("scales", 2), opt("rotations", 3),
-                              None if col is None else col.reshape(s[4]), opt("xyz_b", 5), opt("opacity_b", 6),
-                              opt("color_w", 7), opt("color_b", 8))
+        return R._views_backward(ctx, ctx.dimg, ctx.dal, g_loss)
 
 
-def _rendered_loss(spec, cams, xyz, opacity, scaling, rotation, shs, *, H, W, use_rgb, sh_degree=3, scale_modifier=1.0, xyz_b=None,
-                   opacity_b=None, color_w=None, color_b=None, sync=True, max_instances=None, per_view_gaussians=False,
-                   geometry_cache=None, depth_bound=None, defer_loss=False):
-    if depth_bound is not None:                        # rasterizer.DepthBoundCache: moving geometry (see rasterize_views)
-        if geometry_cache is not None:
-            raise ValueError("geometry_cache (static geometry) or depth_bound (moving geometry), not both")
-        geometry_cache = depth_bound
-    return _RenderedLoss.apply(spec, geometry_cache, cams, int(H), int(W), int(sh_degree if not use_rgb else 0), float(scale_modifier), bool(use_rgb),
-                               bool(sync), max_instances, bool(per_view_gaussians), bool(defer_loss), xyz, opacity, scaling, rotation, shs, xyz_b,
-                               opacity_b, color_w, color_b)
+def _rendered_loss(spec, cams, xyz, opacity, scaling, rotation, shs, **kw):
+    """kw: rasterize_views' keywords (but return_alpha: the fit form renders alpha) and defer_loss."""
+    from . import rasterizer as R
+    return R._apply_views(_RenderedLoss, cams, xyz, opacity, scaling, rotation, shs, return_alpha=spec[0] == "fit", spec=spec, **kw)
 
 
 def rendered_l1_loss(cams, xyz, opacity, scaling, rotation, shs, target, **kw):

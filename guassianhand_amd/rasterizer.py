@@ -15,6 +15,7 @@ there is no PyTorch/CPU fallback — a missing library or a CPU tensor raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import threading
@@ -538,12 +539,22 @@ def _prep(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
 
 
 class _Ctx:
-    __slots__ = ("dims", "inp", "tensors", "ws", "layout", "H", "W", "P", "NV", "M", "wpg", "b_rgb", "rows", "stream", "alpha",
-                 "parent", "radii", "pending", "verdict", "refresh", "l1", "fit", "defer_loss", "__weakref__")
+    """What a forward leaves for its backward and for calls over its tile lists. call: its _Call (the launch's flags: dims.flags)."""
+    __slots__ = ("call", "dims", "inp", "ws", "stream", "alpha", "radii", "parent", "refresh", "pending", "verdict", "l1", "fit",
+                 "defer_loss", "__weakref__")
+
+    def __init__(self, call: _Call, dims, inp, ws, stream, alpha, radii, parent, refresh: bool, l1, fit):
+        self.call, self.dims, self.inp, self.ws, self.stream, self.alpha, self.radii = call, dims, inp, ws, stream, alpha, radii
+        self.parent, self.refresh = parent, refresh
+        self.pending = self.verdict = None             # the counter read-back of a sync-free call (see _forward_full)
+        self.l1 = l1                                   # (loss, dL/dimage) of a fused image loss (GhOutputs.l1_*), else None
+        self.fit = fit                                 # (loss, dL/dimage, dL/dalpha) of a fused fit loss (GhOutputs.fit_loss), else None
+        # GH_FLAG_DEFER_LOSS_SUM: the fused loss's final sum is the backward's to write (GhGrads.deferred_loss)
+        self.defer_loss = bool(dims.flags & _abi.GH_FLAG_DEFER_LOSS_SUM)
 
     def __del__(self):
         try:
-            _ws_release(getattr(self, "ws", None), getattr(self, "stream", 0))
+            _ws_release(self.ws, self.stream)
         except Exception:                      # interpreter shutdown
             pass
 
@@ -612,23 +623,11 @@ def _prepare_call(dev, cams, means3D, opacities, scales, rotations, H, W, shs, c
     return _Call(t, rows, NV, P, M, flags, wpg, b_rgb, split, int(H), int(W), int(sh_degree), float(scale_modifier), cams)
 
 
-def _inputs_struct(c: _Call, with_shs: bool = True, bound=None):
+def _inputs_struct(c: _Call, bound=None):
     t = c.t
     return _abi.GhInputs(_ptr(t["cams"]), _ptr(t["means3D"]), _ptr(t["opacities"]), _ptr(t["scales"]), _ptr(t["rotations"]),
-                         _ptr(t["shs"]) if with_shs else None, _ptr(t["colors_precomp"]), _ptr(t["xyz_b"]), _ptr(t["opacity_b"]),
+                         _ptr(t["shs"]), _ptr(t["colors_precomp"]), _ptr(t["xyz_b"]), _ptr(t["opacity_b"]),
                          _ptr(t["color_w"]), _ptr(t["color_b"]), _ptr(bound), _ptr(t["cov3D"]))
-
-
-def _make_ctx(c: _Call, dims, inp, ws, stream, alpha, parent, radii, pending, verdict, refresh, l1=None, fit=None, defer=False) -> _Ctx:
-    ctx = _Ctx()
-    ctx.dims, ctx.inp, ctx.tensors, ctx.ws, ctx.H, ctx.W, ctx.P, ctx.NV, ctx.M, ctx.wpg = dims, inp, c.t, ws, c.H, c.W, c.P, c.NV, c.M, c.wpg
-    ctx.b_rgb, ctx.rows, ctx.alpha, ctx.parent, ctx.radii, ctx.stream = c.b_rgb, c.rows, alpha, parent, radii, stream
-    ctx.pending, ctx.verdict, ctx.refresh = pending, verdict, refresh
-    ctx.l1 = l1                                    # (loss, dL/dimage) of a fused image loss (GhOutputs.l1_*), else None
-    ctx.fit = fit                                  # (loss, dL/dimage, dL/dalpha) of a fused fit loss (GhOutputs.fit_loss), else None
-    # GH_FLAG_DEFER_LOSS_SUM: the fused loss's final sum is the backward's to write (GhGrads.deferred_loss)
-    ctx.defer_loss = bool(defer) and (l1 is not None or fit is not None)
-    return ctx
 
 
 def _queue_readback(st: _DeviceState, counters, cap, key, dbound=None, learn24=True) -> _Pending:
@@ -641,19 +640,33 @@ def _queue_readback(st: _DeviceState, counters, cap, key, dbound=None, learn24=T
     return pc
 
 
-def _fused_loss(dev, image, alpha, l1_target, fit_loss, allowed: bool):
-    """GhOutputs' trailing fields for a fused image loss (l1_target / l1_dL_dimage / l1_loss / fit_loss) + what the context keeps:
-    ((loss, dL/dimage) or None, (loss, dL/dimage, dL/dalpha) or None, the four GhOutputs fields). The combinations the library does
-    not fuse (allowed False, or the L1 form with a mask channel, or the fit form without one) yield (None, None, no fields): the caller
-    runs gh_l1_loss / gh_fit_loss on the stored images (loss.py does)."""
-    none = (None, None, (None, None, None, None))
+def _record(st: _DeviceState, counters, cap, key, full: bool, dbound=None) -> Optional[_Pending]:
+    """The record of a sync-free forward. Graph mode: none; its counters are registered for check_overflow (keyed by the workspace's
+    address, so a workspace re-used by later captures is listed once). Else a read-back behind the bounded queue of unchecked ones.
+    full: a full forward, whose depth sort ran (its word says whether GH_FLAG_DEPTH24 holds; a refresh's says nothing about it)."""
+    if _policy.graph_mode:
+        st.graph_counters[counters.data_ptr()] = (counters, cap, key, full)
+        return None
+    if len(st.pending) >= _PENDING_MAX:
+        check_overflow(block=False, dev=st.index)
+        if len(st.pending) >= _PENDING_MAX:
+            check_overflow(block=True, dev=st.index)
+    return _queue_readback(st, counters, cap, key, dbound, full)
+
+
+def _fused_loss(dev, image, alpha, l1_target, fit_loss, allowed: bool, defer_loss: bool):
+    """Is an image loss fused into this call, and is its sum deferred: ((loss, dL/dimage) or None, (loss, dL/dimage, dL/dalpha) or
+    None, GhOutputs' four trailing fields (l1_target / l1_dL_dimage / l1_loss / fit_loss), GH_FLAG_DEFER_LOSS_SUM or 0). The render
+    kernel's epilogue computes the L1 form without a mask channel and the fit form with one, where the call allows it and the module
+    policy is on; elsewhere the caller runs gh_l1_loss / gh_fit_loss on the stored images (loss.py does) and there is no sum to defer."""
     if not allowed or not _policy.fused_loss:
-        return none
+        return None, None, (None, None, None, None), 0
+    defer = _abi.GH_FLAG_DEFER_LOSS_SUM if defer_loss else 0
     if l1_target is not None and alpha is None:
         if l1_target.shape != image.shape or l1_target.dtype is not torch.float32 or not l1_target.is_contiguous():
             raise ValueError("l1_target must be a contiguous float32 (n_views, 3, H, W) tensor")
         l1 = (torch.empty((), dtype=torch.float32, device=dev), torch.empty_like(image))
-        return l1, None, (_ptr(l1_target), _ptr(l1[1]), _ptr(l1[0]), None)
+        return l1, None, (_ptr(l1_target), _ptr(l1[1]), _ptr(l1[0]), None), defer
     if fit_loss is not None and alpha is not None:
         gt_rgb, gt_mask, bbox, lam_l1, lam_m, scale = fit_loss
         NV, _, H, W = image.shape
@@ -663,67 +676,94 @@ def _fused_loss(dev, image, alpha, l1_target, fit_loss, allowed: bool):
         fit = (torch.empty((), dtype=torch.float32, device=dev), torch.empty_like(image), torch.empty_like(alpha))
         rec = _abi.GhFitLoss(_ptr(gt_rgb), _ptr(gt_mask), _ptr(bbox), float(lam_l1), float(lam_m), float(scale), _ptr(fit[1]), _ptr(fit[2]),
                              _ptr(fit[0]))
-        return None, fit, (None, None, None, C.pointer(rec))          # (the pointer object keeps `rec` alive through the call)
-    return none
+        return None, fit, (None, None, None, C.pointer(rec)), defer   # (the pointer object keeps `rec` alive through the call)
+    return None, None, (None, None, None, None), 0
+
+
+def _launch(st, L, dev, c: _Call, flags: int, cap: int, return_alpha: bool, owner: Optional[_Ctx] = None, refresh: bool = False,
+            depth_bound: Optional[DepthBoundCache] = None, bound=None, seen=None, l1_target=None, fit_loss=None, defer_loss=False):
+    """The launch sequence of every forward. owner: the context whose tile lists this call walks (gh_forward_refresh with refresh,
+    else gh_forward_shared); None: a full forward (gh_forward) with radii of its own. depth_bound / bound / seen: a full forward's
+    occlusion bound. Returns (image, device view of the GhCounters — None for a shared call: they are the owner's —, context)."""
+    image = torch.empty(c.NV, 3, c.H, c.W, dtype=torch.float32, device=dev)
+    alpha = torch.empty(c.NV, c.H, c.W, dtype=torch.float32, device=dev) if return_alpha else None
+    # (the library fuses no loss into a call with a depth bound or two streams)
+    l1, fit, loss_fields, defer = _fused_loss(dev, image, alpha, l1_target, fit_loss, depth_bound is None and not c.split, defer_loss)
+    dims = _abi.GhDims(c.P, c.NV, c.H, c.W, c.sh_degree, c.M, c.scale_modifier, flags | defer, cap)
+    nbytes = L.gh_workspace_bytes(C.byref(dims))
+    if nbytes == 0:
+        raise RuntimeError("gh_workspace_bytes rejected the dimensions")
+    # a refresh: the library applies THIS call's layout to the owner's workspace, and the arrays a refresh reads of it (cull_bound,
+    # inst_c) lie behind the ones sized by the colour mode (sh_rgb, dmean_sh, sh_scratch: M != 0): the two calls must agree on it
+    # (ADVICE r3) — and the owner's workspace must span this call's layout
+    if refresh and ((owner.call.M != 0) != (c.M != 0) or owner.ws.numel() < nbytes):
+        raise ValueError("refresh_of: the static lists were built in the other colour mode (shs vs colors_precomp); "
+                         "build them again with this call's colour inputs")
+    stream = _raw_stream(dev)
+    ws = _ws_acquire(st, dev, nbytes, stream)
+    if owner is None:
+        # The launch-order hint in the workspace describes the cameras of the call that left it (DESIGN §5): other cameras (or a buffer
+        # fresh from the allocator) -> GH_FLAG_FRESH_ORDER, the order by this call's own list lengths. Results are the same either way.
+        # (the tensor OBJECT through a weak reference + its version counter: the address of a freed camera tensor is what the caching
+        #  allocator hands to the next one, and so is a freed object's id())
+        # A step being CAPTURED into a graph is replayed over this very buffer with this very camera tensor: from its second replay on
+        # the hint is its own, and the flag would be baked into every replay — never set under capture.
+        prev = getattr(ws, "_gh_cam_sig", None)
+        if (prev is None or prev[0]() is not c.cams_obj or prev[1:] != (c.cams_obj._version, c.NV, c.H, c.W)) \
+                and not torch.cuda.is_current_stream_capturing():
+            dims.flags |= _abi.GH_FLAG_FRESH_ORDER
+        ws._gh_cam_sig = (weakref.ref(c.cams_obj), c.cams_obj._version, c.NV, c.H, c.W)
+        radii = torch.empty(c.NV, c.P, dtype=torch.int32, device=dev)
+    else:
+        radii = owner.radii                   # same geometry, same radii
+    inp = _inputs_struct(c, bound)
+    out = _abi.GhOutputs(_ptr(image), None if owner is not None else _ptr(radii), _ptr(alpha), _ptr(seen),
+                         1.0 + (depth_bound.margin if depth_bound is not None else 0.0),
+                         depth_bound.slack if depth_bound is not None else 0, *loss_fields)
+    fn = L.gh_forward if owner is None else L.gh_forward_refresh if refresh else L.gh_forward_shared
+    with _OnDevice(dev):
+        if owner is not None:
+            rc = fn(C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(owner.ws.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
+                    C.c_void_p(stream))
+        elif _policy.stage_timing:
+            rc = _run_stages(st, L.gh_forward_stages, (C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(ws.data_ptr()), nbytes,
+                                                       C.c_void_p(stream)),
+                             (("preprocess_fwd", _abi.GH_FWD_PREPROCESS), ("binning", _abi.GH_FWD_BINNING), ("render_fwd", _abi.GH_FWD_RENDER)))
+        else:
+            rc = fn(C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"{fn.__name__} failed: {_abi.status_name(rc)}")
+    st.last_ws = ws
+    counters = ws[:16].view(torch.int32) if owner is None or refresh else None
+    return image, counters, _Ctx(c, dims, inp, ws, stream, alpha, radii, owner, refresh, l1, fit)
+
+
+def _fits_owner(g0: _Ctx, c: _Call) -> bool:
+    """A call over the tile lists of `g0` (geometry_of / refresh_of) has its shapes and its Gaussian layout."""
+    o = g0.call
+    return (o.P, o.NV, o.H, o.W, o.rows) == (c.P, c.NV, c.H, c.W, c.rows) and \
+        (g0.dims.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS) == (c.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS)
 
 
 def _forward_shared(st, L, dev, c: _Call, g0: _Ctx, return_alpha: bool):
     """gh_forward_shared: a second call over the lists of `g0` (the reference's mask pass after the RGB pass of a view)."""
-    if c.t["shs"] is not None or (g0.dims.flags & _abi.GH_FLAG_SPLIT_STREAMS) or (g0.P, g0.NV, g0.H, g0.W, g0.rows) != (c.P, c.NV, c.H, c.W, c.rows) or \
-            (g0.dims.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS) != (c.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS):
+    if c.t["shs"] is not None or (g0.dims.flags & _abi.GH_FLAG_SPLIT_STREAMS) or not _fits_owner(g0, c):
         raise ValueError("geometry_of: the second call must have the first one's shapes and precomputed colours")
-    cap = int(g0.dims.max_instances)
-    dims = _abi.GhDims(c.P, c.NV, c.H, c.W, c.sh_degree, c.M, c.scale_modifier, c.flags, cap)
-    nbytes = L.gh_workspace_bytes(C.byref(dims))
-    stream = _raw_stream(dev)
-    ws = _ws_acquire(st, dev, nbytes, stream)
-    image = torch.empty(c.NV, 3, c.H, c.W, dtype=torch.float32, device=dev)
-    alpha = torch.empty(c.NV, c.H, c.W, dtype=torch.float32, device=dev) if return_alpha else None
-    inp = _inputs_struct(c, with_shs=False)
-    out = _abi.GhOutputs(_ptr(image), None, _ptr(alpha))
-    with _OnDevice(dev):
-        rc = L.gh_forward_shared(C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(g0.ws.data_ptr()),
-                                 C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"gh_forward_shared failed: {_abi.status_name(rc)}")
-    st.last_ws = ws
-    # the overflow flag is the geometry owner's; same geometry, same radii; an overflow is the first call's (NaN image here too)
-    ctx = _make_ctx(c, dims, inp, ws, stream, alpha, g0, g0.radii, g0.pending, g0.verdict, False)
+    image, _, ctx = _launch(st, L, dev, c, c.flags, int(g0.dims.max_instances), return_alpha, g0)
+    # the overflow flag is the geometry owner's; an overflow is the first call's (NaN image here too)
+    ctx.pending, ctx.verdict = g0.pending, g0.verdict
     return image, g0.radii, ctx
 
 
 def _forward_refresh(st, L, dev, c: _Call, g0: _Ctx, return_alpha: bool, sync, expect_backward: bool, l1_target=None, fit_loss=None,
                      defer_loss=False):
     """gh_forward_refresh: this call's opacities / colours over the static lists of `g0`."""
-    if not (g0.dims.flags & _abi.GH_FLAG_STATIC_LISTS) or (g0.P, g0.NV, g0.H, g0.W, g0.rows) != (c.P, c.NV, c.H, c.W, c.rows) or \
-            (g0.dims.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS) != (c.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS) or g0.parent is not None:
+    if not (g0.dims.flags & _abi.GH_FLAG_STATIC_LISTS) or not _fits_owner(g0, c) or g0.parent is not None:
         raise ValueError("refresh_of: needs the context of a static_lists forward with this call's shapes")
     cap = int(g0.dims.max_instances)
-    defer = bool(defer_loss) and _policy.fused_loss and ((l1_target is not None and not return_alpha) or (fit_loss is not None and return_alpha))
-    dims = _abi.GhDims(c.P, c.NV, c.H, c.W, c.sh_degree, c.M, c.scale_modifier, c.flags | (_abi.GH_FLAG_DEFER_LOSS_SUM if defer else 0), cap)
-    nbytes = L.gh_workspace_bytes(C.byref(dims))
-    # the library applies THIS call's layout to the owner's workspace, and the arrays a refresh reads of it (cull_bound,
-    # inst_c) lie behind the ones sized by the colour mode (sh_rgb, dmean_sh, sh_scratch: M != 0): the two calls must agree
-    # on it (ADVICE r3) — and the owner's workspace must span this call's layout
-    if (g0.M != 0) != (c.M != 0) or g0.ws.numel() < nbytes:
-        raise ValueError("refresh_of: the static lists were built in the other colour mode (shs vs colors_precomp); "
-                         "build them again with this call's colour inputs")
-    stream = _raw_stream(dev)
-    ws = _ws_acquire(st, dev, nbytes, stream)
-    image = torch.empty(c.NV, 3, c.H, c.W, dtype=torch.float32, device=dev)
-    alpha = torch.empty(c.NV, c.H, c.W, dtype=torch.float32, device=dev) if return_alpha else None
-    inp = _inputs_struct(c)
-    l1, fit, loss_fields = _fused_loss(dev, image, alpha, l1_target, fit_loss, True)
-    out = _abi.GhOutputs(_ptr(image), None, _ptr(alpha), None, 1.0, 0, *loss_fields)
-    with _OnDevice(dev):
-        rc = L.gh_forward_refresh(C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(g0.ws.data_ptr()),
-                                  C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"gh_forward_refresh failed: {_abi.status_name(rc)}")
-    counters = ws[:16].view(torch.int32)
-    st.last_ws = ws
-    pending, auto = None, sync is None
-    gkey = (c.P, c.NV, c.H, c.W, False)
+    image, counters, ctx = _launch(st, L, dev, c, c.flags | _abi.GH_FLAG_STATIC_LISTS, cap, return_alpha, g0, True,
+                                   l1_target=l1_target, fit_loss=fit_loss, defer_loss=defer_loss)
+    auto = sync is None
     if sync is None:
         sync = not expect_backward
     if sync:
@@ -734,18 +774,14 @@ def _forward_refresh(st, L, dev, c: _Call, g0: _Ctx, return_alpha: bool, sync, e
             if w.stale:
                 raise GhStaleGeometryError(_STALE_MSG)
             raise GhOverflowError("the static tile lists were built by a call that overflowed its capacity; caches cleared")
-    elif _policy.graph_mode:
-        st.graph_counters[ws.data_ptr()] = (counters, cap, gkey, False)       # (a refresh: no depth sort ran, nothing to learn about it)
     else:
-        # a refresh whose opacity guard fired (or whose lists an overflow truncated) poisons every later step too: look at
-        # the read-backs that have arrived, so that a stale loop surfaces within two calls instead of _PENDING_MAX
-        check_overflow(block=False, keep_recent=2, dev=st.index)
-        if len(st.pending) >= _PENDING_MAX:
-            check_overflow(block=True, dev=st.index)
-        pc = _queue_readback(st, counters, cap, gkey, learn24=False)      # (no depth sort in a refresh: nothing to learn about it)
+        if not _policy.graph_mode:
+            # a refresh whose opacity guard fired (or whose lists an overflow truncated) poisons every later step too: look at
+            # the read-backs that have arrived, so that a stale loop surfaces within two calls instead of _PENDING_MAX
+            check_overflow(block=False, keep_recent=2, dev=st.index)
+        pc = _record(st, counters, cap, (c.P, c.NV, c.H, c.W, False), False)
         if auto:
-            pending = pc
-    ctx = _make_ctx(c, dims, inp, ws, stream, alpha, g0, g0.radii, pending, None, True, l1, fit, defer)
+            ctx.pending = pc
     return image, g0.radii, ctx
 
 
@@ -758,55 +794,14 @@ def _forward_full(st, L, dev, c: _Call, return_alpha: bool, sync, expect_backwar
     if depth_bound is not None and (static_lists or _policy.graph_mode or P == 0 or NV * H * W < depth_bound.min_pixels):
         depth_bound = None                       # lists that outlive the call / a captured call / a small call: no per-call speculation
     base_flags = c.flags | (_abi.GH_FLAG_STATIC_LISTS if static_lists else 0)
-    # the final sum of a fused image loss inside the backward (only where a loss IS fused: see _fused_loss below)
-    if defer_loss and _policy.fused_loss and depth_bound is None and not c.split and \
-            ((l1_target is not None and not return_alpha) or (fit_loss is not None and return_alpha)):
-        base_flags |= _abi.GH_FLAG_DEFER_LOSS_SUM
     while True:
         cap = int(max_instances) if max_instances is not None else st.capacity.get(key, _initial_capacity(P, NV))
         # three depth-sort passes only for a shape a read-back has shown them to suffice for (_DeviceState.depth24)
         flags = base_flags | (_abi.GH_FLAG_DEPTH24 if st.depth24.get(key) is True else 0)
-        dims = _abi.GhDims(P, NV, H, W, c.sh_degree, c.M, c.scale_modifier, flags, cap)
-        nbytes = L.gh_workspace_bytes(C.byref(dims))
-        if nbytes == 0:
-            raise RuntimeError("gh_workspace_bytes rejected the dimensions")
-        stream = _raw_stream(dev)
-        ws = _ws_acquire(st, dev, nbytes, stream)
-        # The launch-order hint in the workspace describes the cameras of the call that left it: other cameras (or a buffer
-        # fresh from the allocator) -> GH_FLAG_FRESH_ORDER, the order by this call's own list lengths. Results are the same either way.
-        # (the tensor OBJECT through a weak reference + its version counter: the address of a freed camera tensor is what the caching
-        #  allocator hands to the next one, and so is a freed object's id())
-        # A step being CAPTURED into a graph is replayed over this very buffer with this very camera tensor: from its second replay on
-        # the hint is its own, and the flag would be baked into every replay — never set under capture.
-        prev = getattr(ws, "_gh_cam_sig", None)
-        if (prev is None or prev[0]() is not c.cams_obj or prev[1:] != (c.cams_obj._version, NV, H, W)) \
-                and not torch.cuda.is_current_stream_capturing():
-            dims.flags |= _abi.GH_FLAG_FRESH_ORDER
-        ws._gh_cam_sig = (weakref.ref(c.cams_obj), c.cams_obj._version, NV, H, W)
-        image = torch.empty(NV, 3, H, W, dtype=torch.float32, device=dev)
-        radii = torch.empty(NV, P, dtype=torch.int32, device=dev)
-        alpha = torch.empty(NV, H, W, dtype=torch.float32, device=dev) if return_alpha else None
         bound, seen = depth_bound._buffers(dev, NV, H, W, key=(P, bool(c.flags & _abi.GH_FLAG_PER_VIEW_GAUSSIANS), c.cams_obj)) \
             if depth_bound is not None else (None, None)
-        inp = _inputs_struct(c, bound=bound)
-        # fused image loss: the loss and its gradient(s) from the render kernel's epilogue (GhOutputs.l1_* / fit_loss); the
-        # combinations the library does not fuse fall back to gh_l1_loss / gh_fit_loss in loss.py (ctx.l1 / ctx.fit are None)
-        l1, fit, loss_fields = _fused_loss(dev, image, alpha, l1_target, fit_loss, depth_bound is None and not c.split)
-        out = _abi.GhOutputs(_ptr(image), _ptr(radii), _ptr(alpha), _ptr(seen), 1.0 + (depth_bound.margin if depth_bound is not None else 0.0),
-                             depth_bound.slack if depth_bound is not None else 0, *loss_fields)
-        with _OnDevice(dev):
-            fargs = (C.byref(dims), C.byref(inp), C.byref(out), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream))
-            if _policy.stage_timing:
-                rc = _run_stages(st, L.gh_forward_stages, fargs, (("preprocess_fwd", _abi.GH_FWD_PREPROCESS),
-                                                                   ("binning", _abi.GH_FWD_BINNING),
-                                                                   ("render_fwd", _abi.GH_FWD_RENDER)))
-            else:
-                rc = L.gh_forward(*fargs)
-        if rc != 0:
-            raise RuntimeError(f"gh_forward failed: {_abi.status_name(rc)}")
-        counters = ws[:16].view(torch.int32)
-        st.last_ws = ws
-        pending, auto, verdict = None, sync is None, None
+        image, counters, ctx = _launch(st, L, dev, c, flags, cap, return_alpha, depth_bound=depth_bound, bound=bound, seen=seen,
+                                       l1_target=l1_target, fit_loss=fit_loss, defer_loss=defer_loss)
         do_sync = sync
         if do_sync is None:
             # auto: read D back once per shape to size the capacity, then sync-free — but only for calls whose backward will
@@ -815,45 +810,33 @@ def _forward_full(st, L, dev, c: _Call, return_alpha: bool, sync, expect_backwar
             do_sync = (max_instances is None and key not in st.capacity) or not expect_backward
             if not do_sync:
                 check_overflow(block=False, keep_recent=2, dev=st.index)  # an overflow of an earlier sync-free call surfaces at most two calls late
-        if do_sync:
-            w = counter_word(counters.tolist())               # the one host read-back, as in the reference wrapper
-            st.last_D = w.d
-            _learn_depth24(st, key, w.bits, w.d)
-            if w.depth24_failed:                               # the three-pass depth sort does not cover this call's depths
-                if depth_bound is not None:
-                    depth_bound.clear()
-                continue
-            if w.overflow:
-                if max_instances is not None:
-                    raise GhOverflowError(f"tile instances D={w.d} exceed max_instances={cap}")
-                _grow_capacity(st, key, w.need(c.split))       # (above `cap`, the capacity it overflowed)
-                if depth_bound is not None:
-                    depth_bound.clear()                        # (the truncated lists' report is not a bound)
-                continue                                       # (the too-small workspace is simply dropped)
-            if w.bound_miss:                                   # the occlusion bound missed: the same call again, unbounded
-                depth_bound.clear()
-                depth_bound.misses += 1
-                continue
+        if not do_sync:
+            # verdict: the counter read-back of a sync-free call, whoever is to ask for it; an explicit sync=False never blocks
+            # (check_overflow() is the caller's job), an auto call's backward checks it first
+            ctx.verdict = _record(st, counters, cap, key, True, depth_bound)
+            if sync is None:
+                ctx.pending = ctx.verdict
+            return image, ctx.radii, ctx
+        w = counter_word(counters.tolist())                   # the one host read-back, as in the reference wrapper
+        st.last_D = w.d
+        _learn_depth24(st, key, w.bits, w.d)
+        if not (w.depth24_failed or w.overflow or w.bound_miss):
             if max_instances is None and key not in st.capacity:
                 _grow_capacity(st, key, w.need(c.split), floor=1 << 16)
-        elif _policy.graph_mode:
-            # every captured workspace is registered (keyed by its address, so a workspace re-used by later captures is
-            # listed once); check_overflow() reads each of them
-            st.graph_counters[ws.data_ptr()] = (counters, cap, key, True)
-        else:
-            if len(st.pending) >= _PENDING_MAX:
-                check_overflow(block=False, dev=st.index)
-                if len(st.pending) >= _PENDING_MAX:
-                    check_overflow(block=True, dev=st.index)
-            pc = _queue_readback(st, counters, cap, key, depth_bound)
-            verdict = pc
-            if auto:                                       # an explicit sync=False never blocks: check_overflow() is the caller's job
-                pending = pc
-        break
-    # verdict: the counter read-back of a sync-free call, whoever is to ask for it
-    ctx = _make_ctx(c._replace(flags=flags), dims, inp, ws, stream, alpha, None, radii, pending, verdict, False, l1, fit,
-                    bool(flags & _abi.GH_FLAG_DEFER_LOSS_SUM))
-    return image, radii, ctx
+            return image, ctx.radii, ctx
+        ctx.ws = None                                          # (the flagged attempt's workspace is dropped, not pooled)
+        if w.depth24_failed:                                   # the three-pass depth sort does not cover this call's depths
+            if depth_bound is not None:
+                depth_bound.clear()
+        elif w.overflow:
+            if max_instances is not None:
+                raise GhOverflowError(f"tile instances D={w.d} exceed max_instances={cap}")
+            _grow_capacity(st, key, w.need(c.split))           # (above `cap`, the capacity it overflowed)
+            if depth_bound is not None:
+                depth_bound.clear()                            # (the truncated lists' report is not a bound)
+        else:                                                  # the occlusion bound missed: the same call again, unbounded
+            depth_bound.clear()
+            depth_bound.misses += 1
 
 
 def raster_forward(cams, means3D, opacities, scales, rotations, *, H: int, W: int, shs=None, colors_precomp=None,
@@ -908,8 +891,7 @@ def raster_forward(cams, means3D, opacities, scales, rotations, *, H: int, W: in
         if geometry_of is not None:
             return _forward_shared(st, L, dev, c, geometry_of, return_alpha)
         if refresh_of is not None:
-            return _forward_refresh(st, L, dev, c._replace(flags=c.flags | _abi.GH_FLAG_STATIC_LISTS), refresh_of, return_alpha, sync,
-                                    expect_backward, l1_target, fit_loss, defer_loss)
+            return _forward_refresh(st, L, dev, c, refresh_of, return_alpha, sync, expect_backward, l1_target, fit_loss, defer_loss)
         return _forward_full(st, L, dev, c, return_alpha, sync, expect_backward, max_instances, static_lists, depth_bound, l1_target,
                              fit_loss, defer_loss)
 
@@ -920,8 +902,6 @@ def cached_raster_forward(cache: Optional[GeometryCache], cams, means3D, opaciti
     sync=True a refresh that finds an opacity above the lists' bound is re-run as a full call, transparently."""
     if cache is None:
         return raster_forward(cams, means3D, opacities, scales, rotations, **kw)
-    if isinstance(cache, DepthBoundCache):         # moving geometry: a speculative occlusion bound instead of static lists
-        return raster_forward(cams, means3D, opacities, scales, rotations, depth_bound=cache, **kw)
     if kw.get("geometry_of") is not None or kw.get("split_streams"):
         raise ValueError("a GeometryCache call takes neither geometry_of nor split_streams")
     xyz_b = kw.get("xyz_b")
@@ -956,7 +936,8 @@ def raster_backward(ctx: _Ctx, dL_dimage: Optional[torch.Tensor], want_means2D: 
     color_w, color_b} (None = all): the others get a NULL pointer in GhGrads — with no geometry gradient asked for the
     per-Gaussian chain rule is skipped altogether (the one-shot fit trains colour / opacity biases only)."""
     L = _lib.lib()
-    t = ctx.tensors
+    c = ctx.call
+    t = c.t
     dev = t["means3D"].device
     st = _state(dev)
     if ctx.pending is not None and ctx.pending.resolve():
@@ -966,21 +947,21 @@ def raster_backward(ctx: _Ctx, dL_dimage: Optional[torch.Tensor], want_means2D: 
         with st.lock:
             st.geom_last = None                    # the re-run of the step must not be taken for this call's mask pass
         raise ctx.pending.error()
-    P, NV, M = ctx.P, ctx.NV, ctx.M
+    P, NV, M, H, W = c.P, c.NV, c.M, c.H, c.W
     if dL_dimage is None:
-        dL_dimage = torch.zeros(NV, 3, ctx.H, ctx.W, dtype=torch.float32, device=dev)
-    g = dL_dimage.detach().to(torch.float32).reshape(NV, 3, ctx.H, ctx.W).contiguous()
-    ga = None if dL_dalpha is None else dL_dalpha.detach().to(torch.float32).reshape(NV, ctx.H, ctx.W).contiguous()
+        dL_dimage = torch.zeros(NV, 3, H, W, dtype=torch.float32, device=dev)
+    g = dL_dimage.detach().to(torch.float32).reshape(NV, 3, H, W).contiguous()
+    ga = None if dL_dalpha is None else dL_dalpha.detach().to(torch.float32).reshape(NV, H, W).contiguous()
     gs = None if grad_scale is None else grad_scale.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
-    R_ = ctx.rows                                  # rows of the per-Gaussian tensors (P, or NV*P for a pose batch)
+    R_ = c.rows                                  # rows of the per-Gaussian tensors (P, or NV*P for a pose batch)
     # ONE contiguous fp32 block for every gradient the kernels write (the C-ABI takes plain pointers, so they may all point
     # into one allocation): a single torch.empty per backward, and the sharded fit all-reduces `block` as it stands —
     # [4 caller floats | color_w | opacity_b | color_b | xyz_b | means3D | opacities | scales | rotations | colour | (means2D)]:
     # the blend-parameter gradients (what the one-shot fit trains) lead, so the fit reduces a short prefix.
     # Every part starts on a 16-byte boundary (the 48-wide rows are written as float4s).
-    shapes = [("color_w", ((R_, 48) if ctx.wpg else (48,)) if t["color_w"] is not None else None),
+    shapes = [("color_w", ((R_, 48) if c.wpg else (48,)) if t["color_w"] is not None else None),
               ("opacity_b", (R_,) if t["opacity_b"] is not None else None),
-              ("color_b", (R_, 3 if ctx.b_rgb else 48) if t["color_b"] is not None else None),
+              ("color_b", (R_, 3 if c.b_rgb else 48) if t["color_b"] is not None else None),
               ("xyz_b", (3,) if t["xyz_b"] is not None else None),
               ("means3D", (R_, 3)), ("opacities", (R_,)), ("scales", (R_, 3) if t["scales"] is not None else None),
               ("rotations", (R_, 4) if t["rotations"] is not None else None), ("cov3D_precomp", (R_, 6) if t["cov3D"] is not None else None),
@@ -1010,7 +991,7 @@ def raster_backward(ctx: _Ctx, dL_dimage: Optional[torch.Tensor], want_means2D: 
                       dL_dshs=_ptr(o["shs"]), dL_dcolors=_ptr(o["colors_precomp"]), dL_dblend_xyz_b=_ptr(o["xyz_b"]),
                       dL_dblend_opacity_b=_ptr(o["opacity_b"]), dL_dblend_color_w=_ptr(o["color_w"]),
                       dL_dblend_color_b=_ptr(o["color_b"]), upstream_scale=_ptr(gs), dL_dcov3D=_ptr(o["cov3D_precomp"]),
-                      deferred_loss=_ptr((ctx.l1 or ctx.fit)[0]) if getattr(ctx, "defer_loss", False) else None)
+                      deferred_loss=_ptr((ctx.l1 or ctx.fit)[0]) if ctx.defer_loss else None)
     stream = _raw_stream(dev)
     ctx.stream = stream                            # the workspace goes back to the pool of the stream that used it last
     with _OnDevice(dev):
@@ -1051,9 +1032,10 @@ def workspace_views(ctx: _Ctx) -> Dict[str, torch.Tensor]:
     L.gh_workspace_layout(C.byref(ctx.dims), C.byref(lay))
     if ctx.dims.flags & _abi.GH_FLAG_SPLIT_STREAMS:
         raise ValueError("workspace_views: a split call keeps two sets of per-instance arrays; render with split_streams=False")
-    ws, N, cap = ctx.ws, ctx.NV * ctx.P, int(ctx.dims.max_instances)
-    gx, gy = (ctx.W + 15) // 16, (ctx.H + 15) // 16
-    pix = ctx.NV * ctx.H * ctx.W
+    c = ctx.call
+    ws, N, cap = ctx.ws, c.NV * c.P, int(ctx.dims.max_instances)
+    gx, gy = (c.W + 15) // 16, (c.H + 15) // 16
+    pix = c.NV * c.H * c.W
 
     def v(off, nbytes, dtype, *shape):
         return ws[off:off + nbytes].view(dtype).reshape(*shape)
@@ -1061,7 +1043,7 @@ def workspace_views(ctx: _Ctx) -> Dict[str, torch.Tensor]:
     geom = v(lay.geom, N * 64, torch.float32, N, 16)
     sorted_tile = v(lay.keys_a, cap * 4, torch.int32, cap)
     if L.gh_partition_is_per_view(C.byref(ctx.dims)) == 1:      # the keys hold tile ids inside the view: the global id through the payload's view
-        sorted_tile = sorted_tile + (v(lay.vals_a, cap * 4, torch.int32, cap).clamp(0, max(N - 1, 0)) // max(ctx.P, 1)) * (gx * gy)
+        sorted_tile = sorted_tile + (v(lay.vals_a, cap * 4, torch.int32, cap).clamp(0, max(N - 1, 0)) // max(c.P, 1)) * (gx * gy)
     return dict(counters=v(lay.counters, 16, torch.int32, 4), g0=geom[:, 0:4], g1=geom[:, 4:8], gb=geom[:, 8],
                 # (view-space depth and 3-sigma tile rect of every projected Gaussian: the geometry line's last float4, v0.8)
                 depth=geom[:, 13], rect=geom[:, 14].contiguous().view(torch.int32),
@@ -1070,9 +1052,9 @@ def workspace_views(ctx: _Ctx) -> Dict[str, torch.Tensor]:
                 sorted_tile=sorted_tile, sorted_slot=v(lay.sorted_slot, cap * 4, torch.int32, cap),
                 sorted_gid=v(lay.vals_a, cap * 4, torch.int32, cap),
                 inst_r2=v(lay.inst_r2, cap * 8, torch.int32, cap, 2),
-                ranges=v(lay.ranges, ctx.NV * gx * gy * 8, torch.int32, ctx.NV * gx * gy, 2),
-                final_T=v(lay.final_T, pix * 4, torch.float32, ctx.NV, ctx.H, ctx.W),
-                n_contrib=v(lay.n_contrib, pix * 4, torch.int32, ctx.NV, ctx.H, ctx.W))
+                ranges=v(lay.ranges, c.NV * gx * gy * 8, torch.int32, c.NV * gx * gy, 2),
+                final_T=v(lay.final_T, pix * 4, torch.float32, c.NV, c.H, c.W),
+                n_contrib=v(lay.n_contrib, pix * 4, torch.int32, c.NV, c.H, c.W))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1225,52 +1207,71 @@ class GaussianRasterizer(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------
-_GRAD_NAMES = ("means3D", "opacities", "scales", "rotations", "colour", "xyz_b", "opacity_b", "color_w", "color_b")
+# The view-batched autograd nodes, _RasterizeViews (rasterize_views) and loss._RenderedLoss (rendered_*_loss), are applied through
+# _apply_views as node.apply(_ViewArgs, cams, xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b) and share
+# _views_forward / _views_backward. _ViewArgs.spec: the loss node's ("l1", target) or ("fit", gt_rgb, gt_mask, bbox, lambdas, scale).
+_ViewArgs = collections.namedtuple("_ViewArgs", "cache depth_bound H W sh_degree scale_modifier use_rgb sync max_instances return_alpha "
+                                                "per_view defer_loss spec")
+_GRAD_AT = 2        # needs_input_grad[_GRAD_AT:]: the nine Gaussian tensors (behind the _ViewArgs and the cameras)
+_GRAD_NAMES = tuple(("means3D", "opacities", "scales", "rotations", colour, "xyz_b", "opacity_b", "color_w", "color_b")
+                    for colour in ("shs", "colors_precomp"))                                # [use_rgb]
 
 
-def _wanted(needs, use_rgb: bool):
-    """Names of the gradients autograd asks for, from the needs_input_grad flags of the nine tensor arguments."""
-    w = {n for n, need in zip(_GRAD_NAMES, needs) if need}
-    if "colour" in w:
-        w.discard("colour")
-        w.add("colors_precomp" if use_rgb else "shs")
-    return w
+def _apply_views(node, cams, xyz, opacity, scaling, rotation, shs, *, H: int, W: int, use_rgb: bool, sh_degree: int = 3,
+                 scale_modifier: float = 1.0, xyz_b=None, opacity_b=None, color_w=None, color_b=None, sync: bool = True,
+                 max_instances: Optional[int] = None, return_alpha: bool = False, per_view_gaussians: bool = False,
+                 geometry_cache=None, depth_bound: Optional[DepthBoundCache] = None, defer_loss: bool = False, spec=None, who: str = ""):
+    """geometry_cache / depth_bound become (GeometryCache or None, DepthBoundCache or None) here, once: a DepthBoundCache passed as
+    geometry_cache is the depth bound (fit.OneShotFit passes either kind). who: the caller's prefix of the error message."""
+    if depth_bound is not None:
+        if geometry_cache is not None:
+            raise ValueError(who + "geometry_cache (static geometry) or depth_bound (moving geometry), not both")
+    elif isinstance(geometry_cache, DepthBoundCache):
+        geometry_cache, depth_bound = None, geometry_cache
+    a = _ViewArgs(geometry_cache, depth_bound, int(H), int(W), int(sh_degree if not use_rgb else 0), float(scale_modifier), bool(use_rgb),
+                  bool(sync), max_instances, bool(return_alpha), bool(per_view_gaussians), bool(defer_loss), spec)
+    return node.apply(a, cams, xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b)
+
+
+def _views_forward(ctx, a: _ViewArgs, cams, gaussians, l1_target=None, fit_loss=None):
+    xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b = gaussians
+    image, radii, rctx = cached_raster_forward(a.cache, cams, xyz, opacity, scaling, rotation, H=a.H, W=a.W, sh_degree=a.sh_degree,
+                                               scale_modifier=a.scale_modifier, xyz_b=xyz_b, opacity_b=opacity_b, color_w=color_w,
+                                               color_b=color_b, sync=a.sync, max_instances=a.max_instances, return_alpha=a.return_alpha,
+                                               per_view_gaussians=a.per_view, depth_bound=a.depth_bound,
+                                               shs=None if a.use_rgb else shs,
+                                               colors_precomp=shs.reshape(shs.shape[0], 3) if a.use_rgb else None,
+                                               l1_target=l1_target, fit_loss=fit_loss, defer_loss=a.defer_loss)
+    ctx.rctx, ctx.use_rgb = rctx, a.use_rgb
+    # (the backward kernels re-read the inputs through the context's pointers: autograd's version check, see _RasterizeGaussians)
+    ctx.save_for_backward(*[t for t in (cams,) + gaussians if t is not None])
+    ctx.shapes = [None if t is None else t.shape for t in gaussians]
+    ctx.set_materialize_grads(False)             # an output that carries no gradient arrives as None, not as a zero image
+    ctx.mark_non_differentiable(radii)
+    return image, radii, rctx
+
+
+def _views_backward(ctx, dL_dimage, dL_dalpha, grad_scale=None):
+    ctx.saved_tensors                                  # inputs written in place since the forward: autograd's own error
+    names = _GRAD_NAMES[ctx.use_rgb]
+    wanted = {n for n, need in zip(names, ctx.needs_input_grad[_GRAD_AT:]) if need}     # only the gradients autograd asks for
+    g = raster_backward(ctx.rctx, dL_dimage, want_means2D=False, dL_dalpha=dL_dalpha, grad_scale=grad_scale, want=wanted)
+    ctx.rctx = None
+    return (None,) * _GRAD_AT + tuple(g[n].reshape(s) if s is not None and n in g else None for n, s in zip(names, ctx.shapes))
 
 
 class _RasterizeViews(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cache, cams, H, W, sh_degree, scale_modifier, use_rgb, sync, max_instances, want_alpha, per_view, xyz, opacity,
-                scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b):
-        kw = dict(colors_precomp=shs.reshape(shs.shape[0], 3)) if use_rgb else dict(shs=shs)
-        image, radii, rctx = cached_raster_forward(cache, cams, xyz, opacity, scaling, rotation, H=H, W=W, sh_degree=sh_degree,
-                                                   scale_modifier=scale_modifier, xyz_b=xyz_b, opacity_b=opacity_b,
-                                                   color_w=color_w, color_b=color_b, sync=sync, max_instances=max_instances,
-                                                   return_alpha=want_alpha, per_view_gaussians=per_view, **kw)
-        ctx.rctx = rctx
-        ctx.use_rgb = use_rgb
-        ctx.save_for_backward(*[t for t in (cams, xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b) if t is not None])
-        ctx.shapes = [None if t is None else t.shape for t in (xyz, opacity, scaling, rotation, shs, xyz_b, opacity_b, color_w, color_b)]
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)             # an unused output (image or alpha) arrives as None, not as a zero image
-        alpha = rctx.alpha if want_alpha else image.new_zeros(0)
-        if not want_alpha:
+    def forward(ctx, a, cams, *gaussians):
+        image, radii, rctx = _views_forward(ctx, a, cams, gaussians)
+        alpha = rctx.alpha if a.return_alpha else image.new_zeros(0)
+        if not a.return_alpha:
             ctx.mark_non_differentiable(alpha)
         return image, alpha, radii
 
     @staticmethod
     def backward(ctx, grad_image, grad_alpha, _gr):
-        ctx.saved_tensors                                  # inputs written in place since the forward: autograd's own error (see _RasterizeGaussians)
-        if ctx.rctx.alpha is None:
-            grad_alpha = None
-        g = raster_backward(ctx.rctx, grad_image, want_means2D=False, dL_dalpha=grad_alpha,
-                            want=_wanted(ctx.needs_input_grad[11:20], ctx.use_rgb))
-        ctx.rctx = None
-        s = ctx.shapes
-        col = g.get("colors_precomp" if ctx.use_rgb else "shs")
-        opt = lambda k, i: g[k].reshape(s[i]) if (s[i] is not None and k in g) else None
-        return (None,) * 11 + (opt("means3D", 0), opt("opacities", 1), opt("scales", 2), opt("rotations", 3),
-                              None if col is None else col.reshape(s[4]), opt("xyz_b", 5), opt("opacity_b", 6),
-                              opt("color_w", 7), opt("color_b", 8))
+        return _views_backward(ctx, grad_image, grad_alpha if ctx.rctx.alpha is not None else None)
 
 
 def rasterize_views(cams: torch.Tensor, xyz, opacity, scaling, rotation, shs, *, H: int, W: int, use_rgb: bool,
@@ -1289,14 +1290,11 @@ def rasterize_views(cams: torch.Tensor, xyz, opacity, scaling, rotation, shs, *,
     the gradients autograd needs are computed. geometry_cache: see GeometryCache (static Gaussians and cameras);
     depth_bound: see DepthBoundCache (Gaussians that move a little between steps) — one or the other.
     """
-    if depth_bound is not None:
-        if geometry_cache is not None:
-            raise ValueError("rasterize_views: geometry_cache (static geometry) or depth_bound (moving geometry), not both")
-        geometry_cache = depth_bound
-    image, alpha, radii = _RasterizeViews.apply(geometry_cache, cams, int(H), int(W), int(sh_degree if not use_rgb else 0), float(scale_modifier),
-                                 bool(use_rgb), bool(sync), max_instances, bool(return_alpha), bool(per_view_gaussians), xyz, opacity,
-                                 scaling,
-                                 rotation, shs, xyz_b, opacity_b, color_w, color_b)
+    image, alpha, radii = _apply_views(_RasterizeViews, cams, xyz, opacity, scaling, rotation, shs, H=H, W=W, use_rgb=use_rgb,
+                                       sh_degree=sh_degree, scale_modifier=scale_modifier, xyz_b=xyz_b, opacity_b=opacity_b,
+                                       color_w=color_w, color_b=color_b, sync=sync, max_instances=max_instances,
+                                       return_alpha=return_alpha, per_view_gaussians=per_view_gaussians,
+                                       geometry_cache=geometry_cache, depth_bound=depth_bound, who="rasterize_views: ")
     return (image, alpha, radii) if return_alpha else (image, radii)
 
 
