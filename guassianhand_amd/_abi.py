@@ -180,3 +180,21 @@ EXPORTED_SYMBOLS = ("gh_version", "gh_workspace_layout", "gh_workspace_bytes", "
                     "gh_uv_gather_forward", "gh_uv_gather_backward", "gh_uv_scatter_sorted", "gh_adam_reg_step", "gh_reg_total", "gh_adam_reg_step_group", "gh_uv_gather_forward2", "gh_uv_scatter_sorted2",
                     "gh_knn_workspace_bytes", "gh_knn_indices", "gh_knn_mismatch_mask", "gh_l1_loss", "gh_fit_loss",
                     "gh_select_workspace_bytes", "gh_select_rows")
+
+
+# ---- include/gh_metrics.h: image-quality scores (a header of its own, not part of gh_raster.h's versioned surface) ----
+GH_METRICS_CHW = 0
+GH_METRICS_PRED_HWC = 1
+GH_METRICS_GT_HWC = 2
+GH_METRICS_HWC = GH_METRICS_PRED_HWC | GH_METRICS_GT_HWC
+
+METRICS_SYMBOLS = ("gh_image_scores_workspace", "gh_image_scores")
+
+
+def declare_metrics(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_metrics.h declares."""
+    lib.gh_image_scores_workspace.restype = C.c_size_t
+    lib.gh_image_scores_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gh_image_scores.restype = C.c_int
+    lib.gh_image_scores.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_double] + [C.c_void_p] * 3 + \
+        [C.c_size_t, C.c_void_p]
