@@ -198,3 +198,31 @@ def declare_metrics(lib: C.CDLL) -> None:
     lib.gh_image_scores.restype = C.c_int
     lib.gh_image_scores.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_double] + [C.c_void_p] * 3 + \
         [C.c_size_t, C.c_void_p]
+
+
+# ---- include/gh_pool.h: per-cell pooling of point features (a header of its own, as gh_metrics.h is) ----
+GH_POOL_MAX = 0
+GH_POOL_MEAN = 1
+GH_POOL_MAX_CELLS = 8192
+
+POOL_SYMBOLS = ("gh_pool_plan_workspace", "gh_pool_plan", "gh_pool_forward", "gh_pool_backward", "gh_plane_mean_forward",
+                "gh_plane_mean_backward")
+
+
+def declare_pool(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_pool.h declares."""
+    lib.gh_pool_plan_workspace.restype = C.c_size_t
+    lib.gh_pool_plan_workspace.argtypes = [C.c_int, C.c_int]
+    lib.gh_pool_plan.restype = C.c_int
+    lib.gh_pool_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]
+    lib.gh_pool_forward.restype = C.c_int
+    lib.gh_pool_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gh_pool_backward.restype = C.c_int
+    lib.gh_pool_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.gh_plane_mean_forward.restype = C.c_int
+    lib.gh_plane_mean_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gh_plane_mean_backward.restype = C.c_int
+    lib.gh_plane_mean_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
