@@ -10,6 +10,9 @@
 //                      takes a quarter of that range; the (8 x 64) tile crosses LDS so that the channel-first plane is read and
 //                      written in 32-byte runs while the point rows stay 256-byte runs.
 // The bin after the last cell collects points whose index is out of range; they are written zeros and counted nowhere.
+// Maximum (gh_pool.h): ties go to the lowest point index (strict > in the walk and in the quarter combine); a NaN never wins,
+// and a cell whose rows are all NaN in a channel is empty for that channel (value 0, argmax T, no gradient); -inf is an ordinary
+// value, so a cell of -inf alone returns -inf with its first point as argmax. Means propagate NaN and inf as arithmetic does.
 // Only integer LDS atomics (the histogram); every float sum has a fixed order.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -166,7 +169,9 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_fwd_kernel(const float* __
   ghp_walk(order, lo, hi, [&](int p) { return on ? x[(size_t)p * xs + ch] : 0.0f; },
            [&](int p, float v) {
              if (MODE == GH_POOL_MAX) {
-               if (arg == T || v > acc) { acc = v; arg = p; }          // strict: the first of equal values stays
+               // strict: the first of equal values stays. v == v: a NaN is never taken, wherever it sits, so a quarter (and a
+               // cell) of NaNs alone keeps arg == T and counts as empty; -inf is a value like any other and is taken when first.
+               if (v == v && (arg == T || v > acc)) { acc = v; arg = p; }
              } else {
                acc += v;
              }

@@ -9,7 +9,10 @@ cell once (a counting sort); the five calls of a forward then reduce over contig
     plane_mean(c, plan)           (T,C) -> (C, n_cells): the mean per cell, 0 for empty cells (generate_plane_features, :55-66)
 
 Ties of a maximum go to the lowest point index, in the value's argmax and in the gradient (torch_scatter leaves them to a race on
-the GPU). Sums have a fixed order, so values and gradients are bitwise reproducible. A point whose index is outside [0, n_cells)
+the GPU). A NaN never wins a maximum, wherever it sits in its cell; a cell whose rows are all NaN in a channel behaves like an
+empty cell for that channel (value 0, argmax T, gradient nowhere). -inf is an ordinary value: a cell that is all -inf returns -inf
+with its first point as argmax. Means propagate NaN and infinities as arithmetic does. Sums have a fixed order, so values and
+gradients are bitwise reproducible. A point whose index is outside [0, n_cells)
 is skipped — it contributes nothing and receives zeros — and `PoolPlan.check()` raises for it on request (the reference asserts
 with a host synchronisation on every forward).
 
@@ -126,24 +129,23 @@ def _valid(plan: PoolPlan):
 
 
 def _cell_sums(x: torch.Tensor, idx: torch.Tensor, ok, n_cells: int) -> torch.Tensor:
-    src = x if ok is None else x * ok.unsqueeze(1).to(x.dtype)
+    src = x if ok is None else torch.where(ok.unsqueeze(1), x, torch.zeros_like(x))      # not x * ok: a skipped NaN stays unseen
     return x.new_zeros(n_cells, x.shape[1]).index_add(0, idx, src)
 
 
 def _cell_max(x: torch.Tensor, plan: PoolPlan):
     """(values (n_cells,C) with 0 for empty cells — differentiable, the gradient goes to the argmax row only —,
-    argmax (n_cells,C) int64: the lowest point index attaining the maximum, T for empty cells)"""
+    argmax (n_cells,C) int64: the lowest point index attaining the maximum, T for empty cells). A NaN never wins; a cell of
+    NaNs alone is empty for that channel (gh_pool.h)."""
     T, Cc = x.shape
     idx, ok = _valid(plan)
     xd = x.detach()
-    if ok is not None:
-        xd = torch.where(ok.unsqueeze(1), xd, torch.full_like(xd, float("-inf")))
+    seen = ~torch.isnan(xd) if ok is None else ~torch.isnan(xd) & ok.unsqueeze(1)
+    xd = torch.where(seen, xd, torch.full_like(xd, float("-inf")))
     col = idx.unsqueeze(1).expand(T, Cc)
     amax = torch.full((plan.n_cells, Cc), float("-inf"), dtype=x.dtype, device=x.device).scatter_reduce(0, col, xd, "amax", include_self=True)
     pts = torch.arange(T, device=x.device).unsqueeze(1).expand(T, Cc)
-    hit = xd == amax[idx]
-    if ok is not None:
-        hit = hit & ok.unsqueeze(1)
+    hit = (xd == amax[idx]) & seen                 # a cell that is all -inf ties at -inf: its first point
     cand = torch.where(hit, pts, torch.full_like(pts, T))
     arg = torch.full((plan.n_cells, Cc), T, dtype=torch.int64, device=x.device).scatter_reduce(0, col, cand, "amin", include_self=True)
     empty = arg == T
@@ -164,7 +166,7 @@ def _pool_local_ref(x: torch.Tensor, plan: PoolPlan, reduce: str = "max", acc: O
     else:
         raise ValueError(f"reduce must be 'max' or 'mean', got {reduce!r}")
     out = cells.index_select(0, idx)
-    return out if ok is None else out * ok.unsqueeze(1).to(out.dtype)
+    return out if ok is None else torch.where(ok.unsqueeze(1), out, torch.zeros_like(out))
 
 
 def _plane_mean_ref(c: torch.Tensor, plan: PoolPlan, acc: Optional[torch.dtype] = None) -> torch.Tensor:

@@ -19,6 +19,12 @@
  * of channel ch, and the backward sends the cell's whole gradient there. torch_scatter's GPU scatter_max leaves the
  * choice between tied points to a race between atomics. An empty cell has argmax T.
  *
+ * NaN and infinities. A NaN never wins a maximum, wherever it sits in its cell (torch_scatter's rule: it compares val > current
+ * from the lowest value). A cell whose rows are all NaN in a channel behaves like an empty cell for that channel: value 0,
+ * argmax T, gradient nowhere. -inf and +inf are ordinary values: a cell that is all -inf in a channel returns -inf with its
+ * first point as argmax. The means (GH_POOL_MEAN, plane mean) propagate NaN and infinities as float arithmetic does, within
+ * the cell that holds them. A NaN or infinity in a point without a cell is read by nothing.
+ *
  * Sums run over a cell's points in ascending point index, the list cut into at most 4 contiguous parts that are added
  * in part order: no atomics anywhere, so values and gradients are bitwise reproducible run to run.
  *

@@ -283,3 +283,131 @@ def test_pool_arguments_are_validated_before_any_launch(gh_lib_path):
     pb = lambda gp=A, T=T, Cc=Cc, n=n, cs=B, order=D, gx=E, gxs=Cc: L.gh_plane_mean_backward(gp, T, Cc, n, cs, order, gx, gxs, None)
     assert pb(gp=None) == INV and pb(gx=None) == INV and pb(cs=None) == INV and pb(Cc=0) == INV and pb(n=0) == INV
     assert pb(gxs=Cc - 1) == INV and pb(gx=A) == INV
+
+
+# ---- the float64 loop of tests/pool_helpers.py against the restatement, on every case of the edge sweep ------------------------------
+# tests/test_gpu_pool_edges.py compares the kernels with the same loop on the same cases: here the loop and the inputs are proven
+# against the restatement (and the restatement against the loop) before a GPU sees them.
+from tests.pool_helpers import (LADDER, NAN_VALUES, SWEEP, TIE_VALUES, assert_within_or_same_nonfinite, case_id, loop_pool,      # noqa: E402
+                                permute_within_cells, plane_bounds, pool_bounds, sweep_case)
+
+
+def test_the_sweep_holds_every_listed_size_and_the_ladder_is_exact():
+    for axis, want in ((0, {1, 3, 255, 256, 257, 700, 3000}), (1, {1, 16, 63, 64, 65, 100, 130}),
+                       (2, {1, 7, 8, 9, 1023, 1024, 1025, 2500, 8192})):
+        assert want <= {c[axis] for c in SWEEP}, axis
+    assert {c[3] for c in SWEEP} >= {"random", "own_cell", "all_in_first", "all_in_last", "ladder", "all_bad"}
+    assert {c[4] for c in SWEEP} >= {"normal", "grid", "const_col", "dup_rows", "inf", *NAN_VALUES}
+    for case in SWEEP:
+        if case[3] != "ladder":
+            continue
+        s = sweep_case(case)
+        assert s.max.counts[:len(LADDER)].tolist() == list(LADDER), case_id(case)
+        pts = torch.nonzero(s.index == 12).flatten()                                     # the 300-point cell
+        assert len(set((pts // 256).tolist())) >= 3, "a cell's points are spread over several 256-point blocks"
+        if case[6]:
+            bad = (s.index.long() < 0) | (s.index.long() >= s.n)
+            assert bad[[0, 255, 256, 257, s.T - 1]].all() and len(set(s.index[bad].tolist())) == 3
+
+
+def test_the_tie_patterns_of_the_sweep_do_tie():
+    """What makes the bit-for-bit argmax comparisons a test of the tie rule. In a cell of k grid values (7 levels) the maximum is
+    attained once with probability <= (k / 7) (6 / 7)^(k - 1), 4 % at k = 32: the cells of 32 points and more tie in nearly every
+    channel. Identical rows tie in every channel of every cell of two points and more, constant columns in theirs."""
+    seen = set()
+    for case in SWEEP:
+        if case[4] not in TIE_VALUES or case[3] in ("own_cell", "all_bad"):
+            continue
+        s = sweep_case(case)
+        least = 32 if case[4] == "grid" else 2
+        attained = (s.x.double() == s.max.pooled) & (s.max.count_pt > 0).unsqueeze(1)
+        times = torch.zeros(s.n, s.C).index_add_(0, s.index.long().clamp(0, s.n - 1), attained.float())[s.max.counts >= least]
+        if case[4] == "const_col":
+            times = times[:, [0, s.C - 1]]
+        if times.numel():
+            seen.add(case[4])
+            assert (times > 1).float().mean() >= 0.9, case_id(case)
+            assert (s.max.argmax[s.max.counts >= least] < s.T).all()
+    assert seen == set(TIE_VALUES)
+
+
+@pytest.mark.parametrize("case", SWEEP, ids=case_id)
+def test_loop_yardstick_and_restatement_agree_on_the_sweep(case):
+    s = sweep_case(case)
+    plan = PoolPlan(s.index, s.n)
+    assert torch.equal(plan.cell_start, s.max.cell_start) and torch.equal(plan.order, s.max.order)
+    assert torch.equal(plan.counts().long(), s.max.counts)
+    bad = bool(((s.index.long() < 0) | (s.index.long() >= s.n)).any())
+    assert int(plan.flag) == int(bad)
+    # maxima: bit for bit
+    vals, arg = pool._cell_max(s.x, plan)
+    assert torch.equal(arg, s.max.argmax)
+    want = torch.where(arg == s.T, torch.zeros(()), s.x.gather(0, arg.clamp(max=s.T - 1)))
+    assert torch.equal(vals, want) and not torch.isnan(vals).any()
+    x = s.x.clone().requires_grad_(True)
+    out = pool._pool_local_ref(x, plan, "max")
+    assert torch.equal(out.detach(), s.max.pooled.float())
+    out.backward(s.cot)
+    _, bwd, _ = pool_bounds(s.max, "max")
+    assert_within(x.grad, s.max.grad, bwd, "max backward, restatement vs loop")
+    assert (x.grad[~s.max.lands] == 0).all()
+    # means: float32 and float64 restatement, both within the bound of the loop
+    fwd, bwd, _ = pool_bounds(s.mean, "mean")
+    for acc in (None, torch.float64):
+        x = s.x.clone().requires_grad_(True)
+        out = pool._pool_local_ref(x, plan, "mean", acc=acc)
+        assert_within_or_same_nonfinite(out, s.mean.pooled, fwd, f"mean forward, restatement ({acc}) vs loop")
+        out.backward(s.cot.to(out.dtype))
+        assert_within_or_same_nonfinite(x.grad, s.mean.grad, bwd, f"mean backward, restatement ({acc}) vs loop")
+        pf, pb = plane_bounds(s.mean)
+        c = s.x.clone().requires_grad_(True)
+        plane = pool._plane_mean_ref(c, plan, acc=acc)
+        assert plane.shape == (s.C, s.n)
+        assert_within_or_same_nonfinite(plane, s.mean.plane, pf, f"plane forward, restatement ({acc}) vs loop")
+        plane.backward(s.plane_cot.to(plane.dtype))
+        assert_within_or_same_nonfinite(c.grad, s.mean.plane_grad, pb, f"plane backward, restatement ({acc}) vs loop")
+
+
+def test_a_nan_never_wins_a_maximum_and_a_cell_of_nans_is_empty():
+    """The rule of include/gh_pool.h on a cell small enough to read: wherever the NaN sits the maximum is that of the other rows."""
+    nan, inf = float("nan"), float("inf")
+    idx = torch.tensor([0, 1, 0, 2, 0, 1, 7, 3, 3])                       # cell 4 is empty, point 6 has no cell
+    #                   cell 0: rows 0, 2, 4        cell 1: rows 1, 5     cell 2: row 3      cell 3: rows 7, 8
+    x = torch.tensor([[nan, 1.0, 5.0, nan], [nan, 2.0, -inf, nan], [3.0, nan, 5.0, nan], [nan, 4.0, nan, 0.0], [3.0, 0.0, nan, nan],
+                      [nan, nan, -inf, 1.0], [nan, inf, nan, nan], [-inf, -inf, nan, 2.0], [-inf, nan, nan, 2.0]], requires_grad=True)
+    plan = PoolPlan(idx, 5)
+    arg = pool.pool_argmax(x, plan)
+    assert arg.tolist() == [[2, 0, 0, 9], [9, 1, 1, 5], [9, 3, 9, 3], [7, 7, 9, 7], [9, 9, 9, 9]]
+    out = pool_local(x, plan, "max")
+    want = torch.tensor([[3.0, 1.0, 5.0, 0.0], [0.0, 2.0, -inf, 1.0], [3.0, 1.0, 5.0, 0.0], [0.0, 4.0, 0.0, 0.0], [3.0, 1.0, 5.0, 0.0],
+                         [0.0, 2.0, -inf, 1.0], [0.0, 0.0, 0.0, 0.0], [-inf, -inf, 0.0, 2.0], [-inf, -inf, 0.0, 2.0]])
+    assert torch.equal(out.detach(), want)
+    out.backward(torch.ones(9, 4))
+    grad = torch.zeros(9, 4)
+    for c, row in enumerate(arg.tolist()):
+        for ch, p in enumerate(row):
+            if p < 9:
+                grad[p, ch] = float((idx == c).sum())
+    assert torch.equal(x.grad, grad)
+    lp = loop_pool(x, idx, 5, "max", torch.ones(9, 4))
+    assert torch.equal(lp.argmax, arg) and torch.equal(lp.pooled.float(), want) and torch.equal(lp.grad.float(), grad)
+    vals, sarg = scatter_max(x.detach().t().unsqueeze(0), idx.reshape(1, 1, 9), dim_size=5)
+    assert torch.equal(sarg[0].t(), arg) and not torch.isnan(vals).any()
+    mean = pool_local(x.detach(), plan, "mean")                          # means propagate, inside the cell and nowhere else
+    assert torch.isnan(mean[[0, 2, 4], 0]).all() and (mean[6] == 0).all() and (mean[[7, 8], 3] == 2.0).all()
+    assert torch.equal(torch.isnan(mean[3]), torch.isnan(x.detach()[3]))
+    assert (plane_mean(x.detach(), plan)[:, 4] == 0).all()
+
+
+@pytest.mark.parametrize("case", [c for c in SWEEP if c[4] in NAN_VALUES], ids=case_id)
+def test_the_maximum_does_not_depend_on_where_a_nan_sits_in_its_cell(case):
+    s = sweep_case(case)
+    plan = PoolPlan(s.index, s.n)
+    assert torch.isnan(s.x).any()
+    out, empty = pool_local(s.x, plan, "max"), pool.pool_argmax(s.x, plan) == s.T
+    for seed in (1, 2):
+        y = permute_within_cells(s.index, s.x, s.n, seed)
+        assert not torch.equal(torch.isnan(y), torch.isnan(s.x)) or case[4] in ("nan_all", "nan_bad")
+        assert torch.equal(pool_local(y, plan, "max"), out) and torch.equal(pool.pool_argmax(y, plan) == s.T, empty)
+        lp = loop_pool(y, s.index, s.n, "max")
+        assert torch.equal(lp.pooled, s.max.pooled) and torch.equal(lp.argmax, pool.pool_argmax(y, plan))
