@@ -226,3 +226,31 @@ def declare_pool(lib: C.CDLL) -> None:
     lib.gh_plane_mean_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gh_plane_mean_backward.restype = C.c_int
     lib.gh_plane_mean_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+
+
+# ---- include/gh_head.h: the fused Gaussian head (a header of its own, as gh_pool.h is) ----
+GH_HEAD_USE_RGB = 1
+GH_HEAD_XYZ_OFFSET = 2
+GH_HEAD_RESTRICT_OFFSET = 4
+GH_HEAD_CLIP_SCALING = 8
+GH_HEAD_ROWS = 64
+GH_HEAD_SEGMENTS = 16
+GH_HEAD_MAX_O = 59
+
+HEAD_SYMBOLS = ("gh_head_workspace_bytes", "gh_head_forward", "gh_head_backward")
+
+
+class GhHeadDesc(C.Structure):
+    _fields_ = [("shs_width", C.c_int32), ("flags", C.c_uint32), ("clip_scaling", C.c_float)]
+
+
+def declare_head(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_head.h declares."""
+    lib.gh_head_workspace_bytes.restype = C.c_size_t
+    lib.gh_head_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gh_head_forward.restype = C.c_int
+    lib.gh_head_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GhHeadDesc)] + \
+        [C.c_void_p] * 6 + [C.c_void_p]
+    lib.gh_head_backward.restype = C.c_int
+    lib.gh_head_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(GhHeadDesc)] + \
+        [C.c_void_p] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -5,6 +5,10 @@ config/config_one_shot.yaml:175 (the string is resolved by tgs.find, tgs/__init_
 tgs.models.renderer_one_shot_edit.GS3DRenderer, whose forward_single_batch takes `render_edit` and per-Gaussian colour weights,
 renderer_one_shot_edit.py:440-520).
 
+`GS3DRendererFusedHead` / `GS3DRendererEditFusedHead` are the same two classes whose `configure()` additionally calls
+`gs_head.fuse_gs_head(self)`: `forward_gs` then ends in the fused Gaussian head (include/gh_head.h) instead of GSLayer's five
+nn.Linear calls and their elementwise launches. Opt-in: the two names above keep the reference's GSLayer.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
@@ -22,5 +26,17 @@ def __getattr__(name):
             from tgs.models.renderer_one_shot_edit import GS3DRenderer as base
             from .renderer import fused_renderer_cls_edit
             _cache[name] = fused_renderer_cls_edit(base)
+        return _cache[name]
+    if name in ("GS3DRendererFusedHead", "GS3DRendererEditFusedHead"):
+        if name not in _cache:
+            base = __getattr__(name[:-len("FusedHead")])
+            from .gs_head import fuse_gs_head
+
+            def configure(self, *args, **kwargs):
+                base.configure(self, *args, **kwargs)
+                fuse_gs_head(self)
+
+            _cache[name] = type(base.__name__, (base,), {"configure": configure, "__module__": __name__,
+                                                         "__doc__": f"{base.__doc__}, and the fused Gaussian head"})
         return _cache[name]
     raise AttributeError(name)
