@@ -254,3 +254,39 @@ def declare_head(lib: C.CDLL) -> None:
     lib.gh_head_backward.restype = C.c_int
     lib.gh_head_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(GhHeadDesc)] + \
         [C.c_void_p] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+# ---- include/gh_vert.h: the fused vertex MLP block (a header of its own, as gh_head.h is) ----
+GH_VERT_ACT_SIGMOID = 0
+GH_VERT_ACT_TANH_OFFSET = 1
+GH_VERT_ROWS = 64
+GH_VERT_SEGMENTS = 16
+GH_VERT_MAX_CF = 256
+
+VERT_SYMBOLS = ("gh_vert_workspace_bytes", "gh_vert_forward", "gh_vert_backward")
+VERT_PARAMS = ("ln_weight", "ln_bias", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias", "fc_weight", "fc_bias")
+
+
+class GhVertDesc(C.Structure):
+    _fields_ = [("K", C.c_int32), ("act", C.c_uint32), ("radius", C.c_float), ("eps", C.c_float)]
+
+
+class GhVertParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VERT_PARAMS]
+
+
+class GhVertGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VERT_PARAMS]
+
+
+def declare_vert(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_vert.h declares."""
+    lib.gh_vert_workspace_bytes.restype = C.c_size_t
+    lib.gh_vert_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.gh_vert_forward.restype = C.c_int
+    lib.gh_vert_forward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(GhVertParams), C.POINTER(GhVertDesc),
+                                    C.c_void_p, C.c_void_p]
+    lib.gh_vert_backward.restype = C.c_int
+    lib.gh_vert_backward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(GhVertParams), C.POINTER(GhVertDesc),
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(GhVertGrads), C.c_void_p, C.c_size_t,
+                                     C.c_void_p]

@@ -9,6 +9,11 @@ renderer_one_shot_edit.py:440-520).
 `gs_head.fuse_gs_head(self)`: `forward_gs` then ends in the fused Gaussian head (include/gh_head.h) instead of GSLayer's five
 nn.Linear calls and their elementwise launches. Opt-in: the two names above keep the reference's GSLayer.
 
+`GS3DRendererFusedGate` / `GS3DRendererEditFusedGate`: `configure()` additionally calls `vert_mlp.fuse_vert_mlps(self)` — the
+validity gate (`gs_valid`) and the position refinement (`vert_pos_refinement`) then run the fused vertex MLP block
+(include/gh_vert.h) while their dropout is inactive (eval mode); in train mode they keep the reference's torch forward.
+`GS3DRendererFusedAll` / `GS3DRendererEditFusedAll`: gate, refinement and head. All opt-in.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
@@ -39,4 +44,21 @@ def __getattr__(name):
             _cache[name] = type(base.__name__, (base,), {"configure": configure, "__module__": __name__,
                                                          "__doc__": f"{base.__doc__}, and the fused Gaussian head"})
         return _cache[name]
+    for suffix, gate, head in (("FusedGate", True, False), ("FusedAll", True, True)):
+        if name in ("GS3DRenderer" + suffix, "GS3DRendererEdit" + suffix):
+            if name not in _cache:
+                base = __getattr__(name[:-len(suffix)])
+                from .gs_head import fuse_gs_head
+                from .vert_mlp import fuse_vert_mlps
+
+                def configure(self, *args, _base=base, _head=head, **kwargs):
+                    _base.configure(self, *args, **kwargs)
+                    fuse_vert_mlps(self)
+                    if _head:
+                        fuse_gs_head(self)
+
+                _cache[name] = type(base.__name__, (base,), {"configure": configure, "__module__": __name__,
+                                                             "__doc__": f"{base.__doc__}, and the fused gate and refinement" +
+                                                                        (" and Gaussian head" if head else "")})
+            return _cache[name]
     raise AttributeError(name)
