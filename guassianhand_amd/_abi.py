@@ -96,7 +96,7 @@ def status_name(code: int) -> str:
     return _STATUS.get(code, f"GH_ERR({code})")
 
 
-def declare(lib: C.CDLL) -> None:
+def declare_raster(lib: C.CDLL) -> None:
     """Attach argtypes/restypes for every symbol include/gh_raster.h declares."""
     lib.gh_version.restype = C.c_int
     lib.gh_version.argtypes = []
@@ -290,3 +290,12 @@ def declare_vert(lib: C.CDLL) -> None:
     lib.gh_vert_backward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(GhVertParams), C.POINTER(GhVertDesc),
                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(GhVertGrads), C.c_void_p, C.c_size_t,
                                      C.c_void_p]
+
+
+ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS
+
+
+def declare(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol of the five headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert):
+        one(lib)

@@ -12,33 +12,25 @@
 //                     columns, and the tile's 64 rows are summed in ascending row order -> one partial per workgroup in the workspace.
 //   reduce    16 elements x 16 runs of partials per workgroup: a run is summed in workgroup order, the 16 runs in run order.
 // No atomics; every float sum has a fixed order that depends on (Cin, O) — and, for grad_W / grad_b, on P — alone.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
 #include "../../include/gh_head.h"
+#include "../csrc_rows/gh_rows.h"
 
-#define GHH_BLOCK 256
+#define GHH_BLOCK GHR_BLOCK
 #define GHH_ROWS GH_HEAD_ROWS
 #define GHH_KC 128             // feature columns per pass through LDS
 #define GHH_XP (GHH_KC + 1)    // pitch of the x tile: odd, so lane = row is conflict-free
 #define GHH_GP (GHH_ROWS + 4)  // pitch of the transposed gradient tile: 16-byte aligned rows
-#define GHH_RED_EL 16          // elements per workgroup of the reduction
 #define GHH_EPS 1e-12f         // F.normalize's floor
 #define GHH_MAX_CIN (1 << 20)  // O * Cin stays far inside an int
 
 static_assert(GHH_ROWS == 64 && GHH_BLOCK == 4 * GHH_ROWS, "lane = row in the forward; 16 rows per wave in the backward");
+static_assert(GH_HEAD_SEGMENTS == GHR_SEGMENTS, "the header documents the shared reduction's run count");
 
 struct GhhOut {  // the contiguous arrays of one direction, and which of them may be accessed 16 bytes at a time
   float *xyz, *scaling, *rotation, *opacity, *shs, *raw;
   unsigned vec;
 };
 enum { GHH_V_XYZ = 1, GHH_V_SCALING = 2, GHH_V_ROTATION = 4, GHH_V_OPACITY = 8, GHH_V_SHS = 16, GHH_V_RAW = 32 };
-
-static inline size_t ghh_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline bool ghh_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-__device__ __forceinline__ float ghh_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // n floats of a tile's contiguous run of an output: 16-byte stores where the run's base allows, the tail element by element
 template <class F>
@@ -54,26 +46,6 @@ __device__ __forceinline__ void ghh_store_run(float* __restrict__ dst, int n, bo
     }
   } else {
     for (int e = tid; e < n; e += GHH_BLOCK) dst[e] = f(e);
-  }
-}
-
-// columns [k0, k0 + kc) of the tile's rows -> s_x[row * GHH_XP + col]; rows past the end of x are zeros
-__device__ __forceinline__ void ghh_stage_x(float* __restrict__ s_x, const float* __restrict__ x, long long x_stride, long long row0,
-                                            int nrows, int k0, int kc, int vec_x, int tid) {
-  if (vec_x) {  // Cin, x_stride multiples of 4 and x 16-byte aligned: so is every row, and kc is a multiple of 4
-    const int q = kc >> 2;
-    for (int i = tid; i < GHH_ROWS * q; i += GHH_BLOCK) {
-      const int r = i / q, c = 4 * (i - r * q);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < nrows) v = *(const float4*)(x + (row0 + r) * x_stride + k0 + c);
-      float* d = s_x + r * GHH_XP + c;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-  } else {
-    for (int i = tid; i < GHH_ROWS * kc; i += GHH_BLOCK) {
-      const int r = i / kc, c = i - r * kc;
-      s_x[r * GHH_XP + c] = r < nrows ? x[(row0 + r) * x_stride + k0 + c] : 0.f;
-    }
   }
 }
 
@@ -103,7 +75,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
   for (int k0 = 0; k0 < Cin; k0 += GHH_KC) {
     const int kc = Cin - k0 < GHH_KC ? Cin - k0 : GHH_KC;
     if (k0) __syncthreads();
-    ghh_stage_x(s_x, x, x_stride, row0, nrows, k0, kc, vec_x, tid);
+    ghr_stage(s_x, GHH_XP, x, x_stride, row0, GHH_ROWS, nrows, k0, kc, vec_x, tid);
     __syncthreads();
     const float* xr = s_x + lane * GHH_XP;
     const int k4 = kc & ~3, tail = kc & 3;
@@ -152,7 +124,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
     if (!xyz_off) return p;
     const int r = e / 3;
     float v = s_raw[r * RP + (e - 3 * r)];
-    if (restrict_off) v = (ghh_sigmoid(v) - 0.5f) * max_step;
+    if (restrict_off) v = (ghr_sigmoid(v) - 0.5f) * max_step;
     return v + p;
   });
   ghh_store_run(out.scaling + row0 * 3, nrows * 3, out.vec & GHH_V_SCALING, tid, [&](int e) {
@@ -172,11 +144,11 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
       dst[0] = a / den; dst[1] = bq / den; dst[2] = c / den; dst[3] = d / den;
     }
   }
-  ghh_store_run(out.opacity + row0, nrows, out.vec & GHH_V_OPACITY, tid, [&](int e) { return ghh_sigmoid(s_raw[e * RP + 10]); });
+  ghh_store_run(out.opacity + row0, nrows, out.vec & GHH_V_OPACITY, tid, [&](int e) { return ghr_sigmoid(s_raw[e * RP + 10]); });
   ghh_store_run(out.shs + row0 * width, nrows * width, out.vec & GHH_V_SHS, tid, [&](int e) {
     const int r = e / width;
     const float v = s_raw[r * RP + 11 + (e - r * width)];
-    return use_rgb ? ghh_sigmoid(v) : v;
+    return use_rgb ? ghr_sigmoid(v) : v;
   });
   if (out.raw) {
     ghh_store_run(out.raw + row0 * O, nrows * O, out.vec & GHH_V_RAW, tid, [&](int e) {
@@ -215,7 +187,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_bwd_kernel(const float* __restr
       if (xyz_off) {
         gx = go;
         if (restrict_off) {
-          const float s = ghh_sigmoid(rt[r * O + c]);
+          const float s = ghr_sigmoid(rt[r * O + c]);
           gx = ((go * max_step) * (1.0f - s)) * s;
         }
       }
@@ -247,7 +219,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_bwd_kernel(const float* __restr
         }
       }
       if (g.opacity) {
-        const float s = ghh_sigmoid(rt[r * O + 10]);
+        const float s = ghr_sigmoid(rt[r * O + 10]);
         gop = (g.opacity[row0 + r] * (1.0f - s)) * s;
       }
     }
@@ -260,7 +232,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_bwd_kernel(const float* __restr
     if (r < nrows && g.shs) {
       gv = g.shs[row0 * width + e];
       if (use_rgb) {
-        const float s = ghh_sigmoid(rt[r * O + 11 + c]);
+        const float s = ghr_sigmoid(rt[r * O + 11 + c]);
         gv = (gv * (1.0f - s)) * s;
       }
     }
@@ -312,7 +284,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_bwd_kernel(const float* __restr
     for (int k0 = 0; k0 < Cin; k0 += GHH_KC) {
       const int kc = Cin - k0 < GHH_KC ? Cin - k0 : GHH_KC;
       if (k0) __syncthreads();
-      ghh_stage_x(s_x, x, x_stride, row0, nrows, k0, kc, vec_x, tid);
+      ghr_stage(s_x, GHH_XP, x, x_stride, row0, GHH_ROWS, nrows, k0, kc, vec_x, tid);
       __syncthreads();
 #pragma unroll 1
       for (int ob = wave * 4; ob < O; ob += 16) {
@@ -356,24 +328,9 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_bwd_kernel(const float* __restr
 // the partials of the nblk workgroups, in workgroup order: GH_HEAD_SEGMENTS contiguous runs, each summed in order, then the runs in order
 __global__ __launch_bounds__(GHH_BLOCK) void ghh_reduce_kernel(const float* __restrict__ part_W, const float* __restrict__ part_b, int nblk,
                                                                int OC, int O, float* __restrict__ grad_W, float* __restrict__ grad_b) {
-  __shared__ float s_red[GH_HEAD_SEGMENTS][GHH_RED_EL];
-  const int tid = threadIdx.x, el = blockIdx.x * GHH_RED_EL + (tid & (GHH_RED_EL - 1)), seg = tid / GHH_RED_EL;
-  const int per = (nblk + GH_HEAD_SEGMENTS - 1) / GH_HEAD_SEGMENTS;
-  const int lo = seg * per, hi = lo + per < nblk ? lo + per : nblk;
-  float s = 0.f;
-  if (el < OC) {
-    for (int i = lo; i < hi; ++i) s += part_W[(size_t)i * OC + el];
-  } else if (el < OC + O) {
-    for (int i = lo; i < hi; ++i) s += part_b[(size_t)i * O + (el - OC)];
-  }
-  s_red[seg][tid & (GHH_RED_EL - 1)] = s;
-  __syncthreads();
-  if (tid < GHH_RED_EL && el < OC + O) {
-    float t = 0.f;
-    for (int q = 0; q < GH_HEAD_SEGMENTS; ++q) t += s_red[q][tid];
-    if (el < OC) grad_W[el] = t;
-    else grad_b[el - OC] = t;
-  }
+  ghr_reduce(
+      nblk, OC + O, [&](int i, int el) { return el < OC ? part_W[(size_t)i * OC + el] : part_b[(size_t)i * O + (el - OC)]; },
+      [&](int el, float t) { *(el < OC ? grad_W + el : grad_b + (el - OC)) = t; });
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
@@ -392,7 +349,7 @@ static int ghh_check_desc(const GhHeadDesc* d) {
 extern "C" size_t gh_head_workspace_bytes(int P, int Cin, int O) {
   if (P < 1 || Cin < 1 || Cin > GHH_MAX_CIN || O < 11 || O > GH_HEAD_MAX_O || !ghh_width_ok(O - 11)) return 0;
   const size_t nb = (size_t)ghh_blocks(P);
-  return ghh_align(nb * (size_t)O * (size_t)Cin * sizeof(float)) + ghh_align(nb * (size_t)O * sizeof(float));
+  return ghr_align(nb * (size_t)O * (size_t)Cin * sizeof(float)) + ghr_align(nb * (size_t)O * sizeof(float));
 }
 
 extern "C" int gh_head_forward(const float* x, int64_t x_stride, int P, int Cin, const float* pts, const float* W, const float* b,
@@ -405,9 +362,9 @@ extern "C" int gh_head_forward(const float* x, int64_t x_stride, int P, int Cin,
   if (!x || !pts || !W || !b || !xyz || !scaling || !rotation || !opacity || !shs) return GH_ERR_INVALID_ARG;
   const int width = desc->shs_width, O = 11 + width;
   GhhOut out = {xyz, scaling, rotation, opacity, shs, raw, 0u};
-  out.vec = (ghh_al16(xyz) ? GHH_V_XYZ : 0u) | (ghh_al16(scaling) ? GHH_V_SCALING : 0u) | (ghh_al16(rotation) ? GHH_V_ROTATION : 0u) |
-            (ghh_al16(opacity) ? GHH_V_OPACITY : 0u) | (ghh_al16(shs) ? GHH_V_SHS : 0u) | (raw && ghh_al16(raw) ? GHH_V_RAW : 0u);
-  const int vec_x = ghh_al16(x) && Cin % 4 == 0 && x_stride % 4 == 0;
+  out.vec = (ghr_al16(xyz) ? GHH_V_XYZ : 0u) | (ghr_al16(scaling) ? GHH_V_SCALING : 0u) | (ghr_al16(rotation) ? GHH_V_ROTATION : 0u) |
+            (ghr_al16(opacity) ? GHH_V_OPACITY : 0u) | (ghr_al16(shs) ? GHH_V_SHS : 0u) | (raw && ghr_al16(raw) ? GHH_V_RAW : 0u);
+  const int vec_x = ghr_al16(x) && Cin % 4 == 0 && x_stride % 4 == 0;
   const size_t lds = (size_t)(GHH_ROWS * GHH_XP + GHH_ROWS * (O | 1)) * sizeof(float);
   const dim3 grid((unsigned)ghh_blocks(P)), block(GHH_BLOCK);
   hipStream_t s = (hipStream_t)hip_stream;
@@ -441,13 +398,13 @@ extern "C" int gh_head_backward(const float* raw, const float* x, int64_t x_stri
   if (wgrad) {
     if (!x || x_stride < Cin) return GH_ERR_INVALID_ARG;
     const size_t need = gh_head_workspace_bytes(P, Cin, O);
-    if (!workspace || !ghh_al16(workspace)) return GH_ERR_INVALID_ARG;
+    if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
     if (ws_bytes < need) return GH_ERR_WORKSPACE_SMALL;
     part_W = (float*)workspace;
-    part_b = (float*)((char*)workspace + ghh_align((size_t)nb * O * Cin * sizeof(float)));
+    part_b = (float*)((char*)workspace + ghr_align((size_t)nb * O * Cin * sizeof(float)));
   }
   GhhOut g = {(float*)g_xyz, (float*)g_scaling, (float*)g_rotation, (float*)g_opacity, (float*)g_shs, nullptr, 0u};
-  const int vec_x = wgrad && ghh_al16(x) && Cin % 4 == 0 && x_stride % 4 == 0;
+  const int vec_x = wgrad && ghr_al16(x) && Cin % 4 == 0 && x_stride % 4 == 0;
   const size_t lds = (size_t)(O * GHH_GP + (wgrad ? GHH_ROWS * GHH_XP : 0)) * sizeof(float);
   const dim3 grid((unsigned)nb), block(GHH_BLOCK);
   hipStream_t s = (hipStream_t)hip_stream;
@@ -456,7 +413,7 @@ extern "C" int gh_head_backward(const float* raw, const float* x, int64_t x_stri
     hipLaunchKernelGGL(ghh_bwd_kernel<true>, grid, block, lds, s, raw, x, (long long)x_stride, P, Cin, W, O, width, desc->flags,
                        desc->clip_scaling, g, grad_x, (long long)gx_stride, grad_pts, part_W, part_b, vec_x);
     const int OC = O * Cin;
-    hipLaunchKernelGGL(ghh_reduce_kernel, dim3((unsigned)((OC + O + GHH_RED_EL - 1) / GHH_RED_EL)), block, 0, s, (const float*)part_W,
+    hipLaunchKernelGGL(ghh_reduce_kernel, dim3(ghr_reduce_blocks(OC + O)), block, 0, s, (const float*)part_W,
                        (const float*)part_b, nb, OC, O, grad_W, grad_b);
   } else {
     hipLaunchKernelGGL(ghh_bwd_kernel<false>, grid, block, lds, s, raw, x, (long long)x_stride, P, Cin, W, O, width, desc->flags,

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/gh_metrics.h"
+#include "../csrc_rows/gh_rows.h"
 
 #define GHM_BLOCK 256
 #define GHM_WAVES (GHM_BLOCK / 64)
@@ -40,8 +41,6 @@ struct GhmLayout {
   int slots, gx, gy;
 };
 
-static inline size_t ghm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static bool ghm_layout(int NV, int H, int W, GhmLayout* L) {
   if (NV < 1 || H < 1 || W < 1) return false;
   L->slots = ghm_row_slots(H);
@@ -49,9 +48,9 @@ static bool ghm_layout(int NV, int H, int W, GhmLayout* L) {
   L->gy = (H + GHM_TY - 1) / GHM_TY;
   const size_t rows = (size_t)NV * L->slots, tiles = (size_t)NV * L->gx * L->gy;
   L->sse = 0;
-  L->box = ghm_align(L->sse + rows * sizeof(double));
-  L->ssim = ghm_align(L->box + rows * sizeof(int4));
-  L->total = ghm_align(L->ssim + tiles * sizeof(double));
+  L->box = ghr_align(L->sse + rows * sizeof(double));
+  L->ssim = ghr_align(L->box + rows * sizeof(int4));
+  L->total = ghr_align(L->ssim + tiles * sizeof(double));
   return true;
 }
 

@@ -20,13 +20,13 @@
 #include <stdint.h>
 
 #include "../../include/gh_pool.h"
+#include "../csrc_rows/gh_rows.h"
 
 #define GHP_BLOCK 256
 #define GHP_WAVES (GHP_BLOCK / 64)
 #define GHP_SCAN_BLOCK 1024
 #define GHP_PLANE_CELLS 8
 
-static inline size_t ghp_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int ghp_blocks(int T) { return (T + GHP_BLOCK - 1) / GHP_BLOCK; }
 
 __device__ __forceinline__ int ghp_bin(const void* __restrict__ index, int is64, int p, int n_cells) {
@@ -304,8 +304,8 @@ static bool ghp_plan_layout(int T, int n_cells, GhpPlanLayout* L) {
   if (T < 1 || n_cells < 1 || n_cells > GH_POOL_MAX_CELLS) return false;
   L->nb = ghp_blocks(T);
   L->hist = 0;
-  L->bad = ghp_align((size_t)L->nb * (n_cells + 1) * sizeof(int));
-  L->total = ghp_align(L->bad + (size_t)L->nb * sizeof(unsigned));
+  L->bad = ghr_align((size_t)L->nb * (n_cells + 1) * sizeof(int));
+  L->total = ghr_align(L->bad + (size_t)L->nb * sizeof(unsigned));
   return true;
 }
 

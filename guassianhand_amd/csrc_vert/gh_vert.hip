@@ -10,43 +10,21 @@
 //             the LayerNorm's backward in place; rows leave as coalesced runs. With parameter gradients: the tile's 64 rows are
 //             summed in ascending row order into one partial per workgroup; a second launch adds the partials in a fixed order.
 // No atomics; every float sum has a fixed order that depends on (Cf, K) — and, for parameter gradients, on P — alone.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
 #include "../../include/gh_vert.h"
+#include "../csrc_rows/gh_rows.h"
 
-#define GHV_BLOCK 256
+#define GHV_BLOCK GHR_BLOCK
 #define GHV_ROWS GH_VERT_ROWS
 #define GHV_OP 3        // pitch of the output tile (K <= 3)
-#define GHV_RED_EL 16   // elements per workgroup of the reduction
 #define GHV_LDS_MAX (128 * 1024)  // the most LDS a workgroup of the backward takes (a CU has 160 KiB)
 
 static_assert(GHV_ROWS == 64 && GHV_BLOCK == 4 * GHV_ROWS, "lane = row, four waves share a row's columns");
-
-static inline size_t ghv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline bool ghv_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-__device__ __forceinline__ float ghv_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+static_assert(GH_VERT_SEGMENTS == GHR_SEGMENTS, "the header documents the shared reduction's run count");
 
 // the tile's R rows of (x, pts) -> s_z[row * ZP + col]; rows past the end are zeros
 __device__ __forceinline__ void ghv_stage(float* s_z, int ZP, const float* __restrict__ x, long long x_stride,
                                           const float* __restrict__ pts, long long row0, int R, int nrows, int Cf, int vec_x, int tid) {
-  if (vec_x) {  // Cf, x_stride multiples of 4 and x 16-byte aligned: so is every row
-    const int q = Cf >> 2;
-    for (int i = tid; i < R * q; i += GHV_BLOCK) {
-      const int r = i / q, c = 4 * (i - r * q);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < nrows) v = *(const float4*)(x + (row0 + r) * x_stride + c);
-      float* d = s_z + r * ZP + c;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-  } else {
-    for (int i = tid; i < R * Cf; i += GHV_BLOCK) {
-      const int r = i / Cf, c = i - r * Cf;
-      s_z[r * ZP + c] = r < nrows ? x[(row0 + r) * x_stride + c] : 0.f;
-    }
-  }
+  ghr_stage(s_z, ZP, x, x_stride, row0, R, nrows, 0, Cf, vec_x, tid);
   for (int i = tid; i < R * 3; i += GHV_BLOCK) {
     const int r = i / 3, c = i - 3 * r;
     s_z[r * ZP + Cf + c] = r < nrows ? pts[row0 * 3 + i] : 0.f;
@@ -191,7 +169,7 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_fwd_kernel(const float* __restr
   for (int e = tid; e < nrows * K; e += GHV_BLOCK) {  // the tile's contiguous run of the output
     const int r = e / K, c = e - r * K;
     const float v = s_o[r * GHV_OP + c];
-    out[row0 * K + e] = act == GH_VERT_ACT_SIGMOID ? ghv_sigmoid(v) : pts[row0 * 3 + e] + tanhf(v) * radius;
+    out[row0 * K + e] = act == GH_VERT_ACT_SIGMOID ? ghr_sigmoid(v) : pts[row0 * 3 + e] + tanhf(v) * radius;
   }
 }
 
@@ -265,7 +243,7 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
     if (r < nrows && g_out) {
       const float g = g_out[row0 * K + e], v = s_o[r * GHV_OP + c];
       if (act == GH_VERT_ACT_SIGMOID) {
-        const float s = ghv_sigmoid(v);
+        const float s = ghr_sigmoid(v);
         go = (g * (1.0f - s)) * s;
       } else {
         const float t = tanhf(v);
@@ -339,30 +317,19 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
 
 // the partials of the nblk workgroups, in workgroup order: GH_VERT_SEGMENTS contiguous runs, each summed in order, then the runs in order
 __global__ __launch_bounds__(GHV_BLOCK) void ghv_reduce_kernel(const float* __restrict__ part, int nblk, GhvOffsets off, GhVertGrads g) {
-  __shared__ float s_red[GH_VERT_SEGMENTS][GHV_RED_EL];
-  const int T = off.o[8];
-  const int tid = threadIdx.x, el = blockIdx.x * GHV_RED_EL + (tid & (GHV_RED_EL - 1)), seg = tid / GHV_RED_EL;
-  const int per = (nblk + GH_VERT_SEGMENTS - 1) / GH_VERT_SEGMENTS;
-  const int lo = seg * per, hi = lo + per < nblk ? lo + per : nblk;
-  float s = 0.f;
-  if (el < T) {
-    for (int i = lo; i < hi; ++i) s += part[(size_t)i * T + el];
-  }
-  s_red[seg][tid & (GHV_RED_EL - 1)] = s;
-  __syncthreads();
-  if (tid < GHV_RED_EL && el < T) {
-    float t = 0.f;
-    for (int q = 0; q < GH_VERT_SEGMENTS; ++q) t += s_red[q][tid];
-    float* dst = el < off.o[1] ? g.ln_weight + el
-               : el < off.o[2] ? g.ln_bias + (el - off.o[1])
-               : el < off.o[3] ? g.fc1_weight + (el - off.o[2])
-               : el < off.o[4] ? g.fc1_bias + (el - off.o[3])
-               : el < off.o[5] ? g.fc2_weight + (el - off.o[4])
-               : el < off.o[6] ? g.fc2_bias + (el - off.o[5])
-               : el < off.o[7] ? g.fc_weight + (el - off.o[6])
-                               : g.fc_bias + (el - off.o[7]);
-    *dst = t;
-  }
+  ghr_reduce(
+      nblk, off.o[8], [&](int i, int el) { return part[(size_t)i * off.o[8] + el]; },
+      [&](int el, float t) {
+        float* dst = el < off.o[1] ? g.ln_weight + el
+                   : el < off.o[2] ? g.ln_bias + (el - off.o[1])
+                   : el < off.o[3] ? g.fc1_weight + (el - off.o[2])
+                   : el < off.o[4] ? g.fc1_bias + (el - off.o[3])
+                   : el < off.o[5] ? g.fc2_weight + (el - off.o[4])
+                   : el < off.o[6] ? g.fc2_bias + (el - off.o[5])
+                   : el < off.o[7] ? g.fc_weight + (el - off.o[6])
+                                   : g.fc_bias + (el - off.o[7]);
+        *dst = t;
+      });
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
@@ -399,7 +366,7 @@ static void ghv_allow_lds(Kern kern, size_t lds) {
 extern "C" size_t gh_vert_workspace_bytes(int P, int D, int Hd, int K) {
   if (P < 1 || D < 4 || D > GH_VERT_MAX_CF + 3 || Hd != D / 4 || (K != 1 && K != 3)) return 0;
   const int rows = ghv_bwd_rows(D);
-  return ghv_align((size_t)((P + rows - 1) / rows) * (size_t)ghv_offsets(D, Hd, K).o[8] * sizeof(float));
+  return ghr_align((size_t)((P + rows - 1) / rows) * (size_t)ghv_offsets(D, Hd, K).o[8] * sizeof(float));
 }
 
 extern "C" int gh_vert_forward(const float* x, int64_t x_stride, const float* pts, int P, int Cf, const GhVertParams* params,
@@ -409,7 +376,7 @@ extern "C" int gh_vert_forward(const float* x, int64_t x_stride, const float* pt
   if (x_stride < Cf || !x || !pts || !out) return GH_ERR_INVALID_ARG;
   if (P == 0) return GH_OK;
   const int D = Cf + 3, Hd = D / 4, ZP = D | 1, HP = Hd | 1;
-  const int vec_x = ghv_al16(x) && Cf % 4 == 0 && x_stride % 4 == 0;
+  const int vec_x = ghr_al16(x) && Cf % 4 == 0 && x_stride % 4 == 0;
   const size_t lds = (size_t)(2 * GHV_BLOCK + GHV_ROWS * (ZP + HP + GHV_OP)) * sizeof(float);
   hipStream_t s = (hipStream_t)hip_stream;
   (void)hipGetLastError();
@@ -432,11 +399,11 @@ extern "C" int gh_vert_backward(const float* x, int64_t x_stride, const float* p
   if (P == 0) return GH_OK;
   const int K = desc->K, D = Cf + 3, Hd = D / 4, rows = ghv_bwd_rows(D), nb = (P + rows - 1) / rows;
   if (wgrad) {
-    if (!workspace || !ghv_al16(workspace)) return GH_ERR_INVALID_ARG;
+    if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
     if (ws_bytes < gh_vert_workspace_bytes(P, D, Hd, K)) return GH_ERR_WORKSPACE_SMALL;
   }
   const GhvOffsets off = ghv_offsets(D, Hd, K);
-  const int vec_x = ghv_al16(x) && Cf % 4 == 0 && x_stride % 4 == 0;
+  const int vec_x = ghr_al16(x) && Cf % 4 == 0 && x_stride % 4 == 0;
   const size_t lds = ghv_bwd_lds(D, rows);
   const dim3 grid((unsigned)nb), block(GHV_BLOCK);
   hipStream_t s = (hipStream_t)hip_stream;
@@ -449,7 +416,7 @@ extern "C" int gh_vert_backward(const float* x, int64_t x_stride, const float* p
   } while (0)
   if (wgrad) {
     if (rows == GHV_ROWS) GHV_BWD(true, GHV_ROWS); else GHV_BWD(true, GHV_ROWS / 2);
-    hipLaunchKernelGGL(ghv_reduce_kernel, dim3((unsigned)((off.o[8] + GHV_RED_EL - 1) / GHV_RED_EL)), block, 0, s,
+    hipLaunchKernelGGL(ghv_reduce_kernel, dim3(ghr_reduce_blocks(off.o[8])), block, 0, s,
                        (const float*)workspace, nb, off, *grads);
   } else {
     if (rows == GHV_ROWS) GHV_BWD(false, GHV_ROWS); else GHV_BWD(false, GHV_ROWS / 2);

@@ -30,48 +30,18 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi, _lib
+from . import _abi
+from ._call import check_f32, launch, lib, ptr, row_stride, rows, workspace
 from .renderer import GaussianModel, gs_activations
 
 FIELDS = ("xyz", "scaling", "rotation", "opacity", "shs")          # the order of the concatenated rows (gh_head.h)
 _FIXED = {"xyz": 3, "scaling": 3, "rotation": 4, "opacity": 1}
 SHS_WIDTHS = (3, 12, 27, 48)
-_declared = False
-
-
-def _head_lib() -> C.CDLL:
-    global _declared
-    L = _lib.lib()
-    if not _declared:
-        _abi.declare_head(L)
-        _declared = True
-    return L
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ok(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {_abi.status_name(rc)}")
 
 
 def _check(x, pts, weight, bias, shs_width, use_rgb, clip_scaling) -> None:
     """Everything that can be refused on the host is, before any device work."""
-    for name, t, nd in (("x", x, 2), ("pts", pts, 2), ("weight", weight, 2), ("bias", bias, 1)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name}: expected float32, got {t.dtype}")
-        if t.dim() != nd:
-            raise ValueError(f"{name}: expected {nd} dimensions, got {tuple(t.shape)}")
-        if t.device != x.device:
-            raise ValueError(f"{name} is on {t.device}, x on {x.device}")
+    check_f32(x, (("x", x, 2), ("pts", pts, 2), ("weight", weight, 2), ("bias", bias, 1)))
     if int(shs_width) not in SHS_WIDTHS:
         raise ValueError(f"shs_width must be one of {SHS_WIDTHS}, got {shs_width}")
     if use_rgb and int(shs_width) != 3:
@@ -138,34 +108,21 @@ def _desc(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling) -> _abi
     return _abi.GhHeadDesc(int(shs_width), flags, 0.0 if clip_scaling is None else float(clip_scaling))
 
 
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """A (P,C) float32 tensor the kernels read in place: unit column stride, any row stride >= C; anything else is copied once."""
-    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _row_stride(t: torch.Tensor) -> int:
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
 class _GsHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pts, weight, bias, cfg):
         shs_width = cfg[0]
         ctx.set_materialize_grads(False)
-        x, pts, weight, bias = _rows(x.detach()), pts.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
+        x, pts, weight, bias = rows(x.detach()), pts.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
         P, Cin = x.shape
         O, dev = 11 + shs_width, x.device
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         xyz, scaling, rotation, opacity, shs = new(P, 3), new(P, 3), new(P, 4), new(P, 1), new(P, shs_width)
         raw = new(P, O) if any(ctx.needs_input_grad[:4]) else None
         if P > 0:
-            desc = _desc(*cfg)
-            with torch.cuda.device(dev):
-                _ok(_head_lib().gh_head_forward(_ptr(x), _row_stride(x), P, Cin, _ptr(pts), _ptr(weight), _ptr(bias), C.byref(desc),
-                                                _ptr(xyz), _ptr(scaling), _ptr(rotation), _ptr(opacity), _ptr(shs), _ptr(raw),
-                                                _stream(dev)), f"gh_head_forward (P={P}, Cin={Cin}, O={O})")
+            launch("gh_head_forward", dev, ptr(x), row_stride(x), P, Cin, ptr(pts), ptr(weight), ptr(bias), C.byref(_desc(*cfg)),
+                   ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(shs), ptr(raw),
+                   what=f"gh_head_forward (P={P}, Cin={Cin}, O={O})")
         ctx.cfg = cfg
         ctx.save_for_backward(x, weight, raw)
         return xyz, scaling, rotation, opacity, shs
@@ -186,14 +143,11 @@ class _GsHeadFn(torch.autograd.Function):
                 gw.zero_(), gb.zero_()
         else:
             gs = [None if g is None else g.float().contiguous() for g in (g_xyz, g_scaling, g_rotation, g_opacity, g_shs)]
-            L = _head_lib()
-            nbytes = int(L.gh_head_workspace_bytes(P, Cin, O)) if need_w else 0
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if need_w else None
-            desc = _desc(*ctx.cfg)
-            with torch.cuda.device(dev):
-                _ok(L.gh_head_backward(_ptr(raw), _ptr(x), _row_stride(x), P, Cin, _ptr(weight), C.byref(desc), *[_ptr(g) for g in gs],
-                                       _ptr(gx), Cin, _ptr(gpts), _ptr(gw), _ptr(gb), _ptr(ws), nbytes, _stream(dev)),
-                    f"gh_head_backward (P={P}, Cin={Cin}, O={O})")
+            nbytes = int(lib().gh_head_workspace_bytes(P, Cin, O)) if need_w else 0
+            ws = workspace(nbytes, dev) if need_w else None
+            launch("gh_head_backward", dev, ptr(raw), ptr(x), row_stride(x), P, Cin, ptr(weight), C.byref(_desc(*ctx.cfg)),
+                   *[ptr(g) for g in gs], ptr(gx), Cin, ptr(gpts), ptr(gw), ptr(gb), ptr(ws), nbytes,
+                   what=f"gh_head_backward (P={P}, Cin={Cin}, O={O})")
         return (gx if ctx.needs_input_grad[0] else None, gpts, gw if ctx.needs_input_grad[2] else None,
                 gb if ctx.needs_input_grad[3] else None, None)
 

@@ -14,12 +14,11 @@ kernels raise if the library is missing and there is no CPU path.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import torch
 
-from . import _abi, _lib
+from ._call import launch, lib, ptr
 
 
 def _check(points: torch.Tensor) -> torch.Tensor:
@@ -34,18 +33,13 @@ def knn_indices(points: torch.Tensor, K: int, return_dists: bool = False) -> Tup
     """points (B,N,3) -> idx (B,N,K) int32 sorted by (squared distance, index) [, dists (B,N,K)]."""
     p = _check(points)
     B, N, _ = p.shape
-    L = _lib.lib()
     idx = torch.empty(B, N, K, dtype=torch.int32, device=p.device)
     dists = torch.empty(B, N, K, dtype=torch.float32, device=p.device) if return_dists else None
-    nbytes = int(L.gh_knn_workspace_bytes(N))
+    nbytes = int(lib().gh_knn_workspace_bytes(N))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
-    with torch.cuda.device(p.device):
-        stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-        for b in range(B):
-            rc = L.gh_knn_indices(C.c_void_p(p[b].data_ptr()), N, K, C.c_void_p(idx[b].data_ptr()),
-                                  C.c_void_p(dists[b].data_ptr()) if return_dists else None, C.c_void_p(ws.data_ptr()), nbytes, stream)
-            if rc != 0:
-                raise RuntimeError(f"gh_knn_indices failed: {_abi.status_name(rc)} (N={N}, K={K})")
+    for b in range(B):
+        launch("gh_knn_indices", p.device, ptr(p[b]), N, K, ptr(idx[b]), ptr(dists[b]) if return_dists else None, ptr(ws), nbytes,
+               detail=f" (N={N}, K={K})")
     return idx, dists
 
 
@@ -63,13 +57,7 @@ def interaction_mask(pointclouds: torch.Tensor, t_point: torch.Tensor, K: int = 
     a, _ = knn_indices(pointclouds, K)
     b, _ = knn_indices(t_point, K)
     B, N, _ = a.shape
-    L = _lib.lib()
     mask = torch.empty(B, N, dtype=torch.uint8, device=a.device)
-    with torch.cuda.device(a.device):
-        stream = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        for i in range(B):
-            rc = L.gh_knn_mismatch_mask(C.c_void_p(a[i].data_ptr()), C.c_void_p(b[i].data_ptr()), N, K, min_same,
-                                        C.c_void_p(mask[i].data_ptr()), stream)
-            if rc != 0:
-                raise RuntimeError(f"gh_knn_mismatch_mask failed: {_abi.status_name(rc)}")
+    for i in range(B):
+        launch("gh_knn_mismatch_mask", a.device, ptr(a[i]), ptr(b[i]), N, K, min_same, ptr(mask[i]))
     return mask.bool().unsqueeze(-1)

@@ -4,11 +4,9 @@ Counterpart of the L1 term of the reference's loss (utils.py:282-294, `lambda_l1
 bench.py's metric definition. ROCm tensors only; raises if the HIP library is missing."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _abi, _lib
+from ._call import launch, ptr
 
 _N_PARTIALS = 1024
 
@@ -18,7 +16,6 @@ def _l1_kernel(image, target, guard=None):
     forward that rendered `image` (overflow -> loss NaN, zero gradient)."""
     if not image.is_cuda:
         raise RuntimeError("gh_l1_loss runs on a ROCm device only (there is no CPU path)")
-    L = _lib.lib()
     a = image.detach().float().contiguous()
     b = target.detach().float().contiguous()
     if a.shape != b.shape:
@@ -28,13 +25,7 @@ def _l1_kernel(image, target, guard=None):
     grad = torch.empty_like(a)
     nblk = max(1, min(_N_PARTIALS, (n // 4 + 255) // 256))
     partials = torch.empty(nblk, dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        rc = L.gh_l1_loss(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, C.c_void_p(loss.data_ptr()),
-                          C.c_void_p(grad.data_ptr()), C.c_void_p(partials.data_ptr()), nblk,
-                          None if guard is None else C.c_void_p(guard.data_ptr()),
-                          C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gh_l1_loss failed: {_abi.status_name(rc)}")
+    launch("gh_l1_loss", a.device, ptr(a), ptr(b), n, ptr(loss), ptr(grad), ptr(partials), nblk, ptr(guard))
     return loss, grad
 
 
@@ -61,7 +52,6 @@ def _fit_kernel(image, alpha, gt_rgb, gt_mask, bbox_mask, lambda_l1, lambda_mlos
     """(loss, dL/dimage, dL/dalpha) of the fit's image loss from one pass (gh_fit_loss)."""
     if not image.is_cuda:
         raise RuntimeError("gh_fit_loss runs on a ROCm device only (there is no CPU path)")
-    L = _lib.lib()
     f32 = lambda t: None if t is None else t.detach().float().contiguous()
     im, al, gr, gm, bb = f32(image), f32(alpha), f32(gt_rgb), f32(gt_mask), f32(bbox_mask)
     NV, _, H, W = im.shape
@@ -71,13 +61,8 @@ def _fit_kernel(image, alpha, gt_rgb, gt_mask, bbox_mask, lambda_l1, lambda_mlos
     dimg, dal = torch.empty_like(im), torch.empty_like(al)
     nblk = max(1, min(_N_PARTIALS, (NV * H * W + 255) // 256))
     partials = torch.empty(nblk, dtype=torch.float32, device=im.device)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(im.device):
-        rc = L.gh_fit_loss(p(im), p(al), p(gr), p(gm), p(bb), NV, H, W, float(lambda_l1), float(lambda_mloss), float(scale),
-                           p(loss), p(dimg), p(dal), p(partials), nblk, p(guard),
-                           C.c_void_p(torch.cuda.current_stream(im.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gh_fit_loss failed: {_abi.status_name(rc)}")
+    launch("gh_fit_loss", im.device, ptr(im), ptr(al), ptr(gr), ptr(gm), ptr(bb), NV, H, W, float(lambda_l1), float(lambda_mloss),
+           float(scale), ptr(loss), ptr(dimg), ptr(dal), ptr(partials), nblk, ptr(guard))
     return loss, dimg, dal
 
 

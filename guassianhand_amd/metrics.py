@@ -14,16 +14,14 @@ LPIPS and the reference's PNG dumps of the crops are not computed. CPU tensors g
 torch restatement of the same four steps (the yardstick of the GPU tests); ROCm tensors go through the HIP kernels only."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import _abi, _lib
-
-_declared = False
+from . import _abi
+from ._call import launch, lib, ptr, workspace
 
 
 class ImageScores(NamedTuple):
@@ -31,15 +29,6 @@ class ImageScores(NamedTuple):
     psnr: torch.Tensor       # (Nv,) float64
     ssim: torch.Tensor       # (Nv,) float64, NaN where the crop is smaller than 7x7
     bbox: torch.Tensor       # (Nv, 4) int32: x, y, w, h of mask_at_box's bounding box, (0, 0, 0, 0) for an empty mask
-
-
-def _metrics_lib() -> C.CDLL:
-    global _declared
-    L = _lib.lib()
-    if not _declared:
-        _abi.declare_metrics(L)
-        _declared = True
-    return L
 
 
 def _images(t: torch.Tensor, layout: str, name: str):
@@ -95,18 +84,12 @@ def image_scores(pred: torch.Tensor, gt: torch.Tensor, mask_at_box: torch.Tensor
         raise ValueError("pred, gt and the masks must be on the same device")
     p, p_hwc = _images(pred, layout, "pred")
     g, g_hwc = _images(gt, layout, "gt")
-    L = _metrics_lib()
-    nbytes = L.gh_image_scores_workspace(Nv, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nbytes = lib().gh_image_scores_workspace(Nv, H, W)
+    ws = workspace(nbytes, dev)
     scores = torch.empty(3, Nv, dtype=torch.float64, device=dev)
     bbox = torch.empty(Nv, 4, dtype=torch.int32, device=dev)
     flags = (_abi.GH_METRICS_PRED_HWC if p_hwc else 0) | (_abi.GH_METRICS_GT_HWC if g_hwc else 0)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = L.gh_image_scores(ptr(p), ptr(g), ptr(mbox), ptr(bbm), Nv, H, W, flags, R, ptr(scores), ptr(bbox), ptr(ws), nbytes,
-                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"gh_image_scores failed: {_abi.status_name(rc)}")
+    launch("gh_image_scores", dev, ptr(p), ptr(g), ptr(mbox), ptr(bbm), Nv, H, W, flags, R, ptr(scores), ptr(bbox), ptr(ws), nbytes)
     return ImageScores(scores[0], scores[1], scores[2], bbox)
 
 

@@ -23,50 +23,25 @@ HIP kernels only. `scatter_max` / `scatter_mean` carry torch_scatter's signature
 on the reference's own class for the `pointcloud_encoder_*_cls` config lines."""
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from . import _abi, _lib
+from . import _abi
+from ._call import launch, lib, ptr, row_stride, rows, workspace
 
-_declared = False
 _REDUCE = {"max": _abi.GH_POOL_MAX, "mean": _abi.GH_POOL_MEAN}
 
 
-def _pool_lib() -> C.CDLL:
-    global _declared
-    L = _lib.lib()
-    if not _declared:
-        _abi.declare_pool(L)
-        _declared = True
-    return L
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ok(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {_abi.status_name(rc)}")
-
-
-def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
-    """A (T,C) float32 tensor the kernels can read in place: unit column stride, any row stride."""
+def _features(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A (T,C) float32 tensor, as the kernels can read it in place (_call.rows)."""
     if t.dim() != 2:
         raise ValueError(f"{name}: expected (T, C), got {tuple(t.shape)}")
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
+    return rows(t)
 
 
 class PoolPlan:
@@ -91,17 +66,14 @@ class PoolPlan:
             self.cell_start = torch.cat([counts.new_zeros(1), counts.cumsum(0)])[:self.n_cells + 1].to(torch.int32)
             self.flag = bad.any().to(torch.int32).reshape(1)
             return
-        L = _pool_lib()
         dev = self.device
         self.cell_start = torch.empty(self.n_cells + 1, dtype=torch.int32, device=dev)
         self.order = torch.empty(self.T, dtype=torch.int32, device=dev)
         self.flag = torch.empty(1, dtype=torch.int32, device=dev)
-        nbytes = int(L.gh_pool_plan_workspace(self.T, self.n_cells))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _ok(L.gh_pool_plan(_ptr(self.index), int(index.dtype == torch.int64), self.T, self.n_cells, _ptr(self.cell_start),
-                               _ptr(self.order), _ptr(self.flag), _ptr(ws), nbytes, _stream(dev)),
-                f"gh_pool_plan (T={self.T}, n_cells={self.n_cells})")
+        nbytes = int(lib().gh_pool_plan_workspace(self.T, self.n_cells))
+        ws = workspace(nbytes, dev)
+        launch("gh_pool_plan", dev, ptr(self.index), int(index.dtype == torch.int64), self.T, self.n_cells, ptr(self.cell_start),
+               ptr(self.order), ptr(self.flag), ptr(ws), nbytes, what=f"gh_pool_plan (T={self.T}, n_cells={self.n_cells})")
 
     def check(self) -> None:
         """Raise if some point's index was outside [0, n_cells) (one device-to-host copy; the reference's assert)."""
@@ -179,27 +151,20 @@ def _plane_mean_ref(c: torch.Tensor, plan: PoolPlan, acc: Optional[torch.dtype] 
 
 # ---- device path ---------------------------------------------------------------------------------------------------------------
 def _launch_pool_forward(x, plan, reduce, out, out_col, argmax):
-    L = _pool_lib()
     T, Cc = x.shape
-    with torch.cuda.device(x.device):
-        _ok(L.gh_pool_forward(_ptr(x), x.stride(0) if T > 1 else Cc, T, Cc, plan.n_cells, _ptr(plan.cell_start), _ptr(plan.order),
-                              _REDUCE[reduce], _ptr(out), out.stride(0) if T > 1 else out.shape[1], out_col, _ptr(argmax),
-                              _stream(x.device)), "gh_pool_forward")
+    launch("gh_pool_forward", x.device, ptr(x), row_stride(x), T, Cc, plan.n_cells, ptr(plan.cell_start), ptr(plan.order),
+           _REDUCE[reduce], ptr(out), row_stride(out), out_col, ptr(argmax))
 
 
 def _launch_pool_backward(g, g_col, Cc, plan, reduce, argmax, gx, accumulate):
-    L = _pool_lib()
-    T = g.shape[0]
-    with torch.cuda.device(g.device):
-        _ok(L.gh_pool_backward(_ptr(g), g.stride(0) if T > 1 else g.shape[1], g_col, T, Cc, plan.n_cells, _ptr(plan.cell_start),
-                               _ptr(plan.order), _REDUCE[reduce], _ptr(argmax), _ptr(gx), gx.stride(0) if T > 1 else Cc,
-                               int(accumulate), _stream(g.device)), "gh_pool_backward")
+    launch("gh_pool_backward", g.device, ptr(g), row_stride(g), g_col, g.shape[0], Cc, plan.n_cells, ptr(plan.cell_start),
+           ptr(plan.order), _REDUCE[reduce], ptr(argmax), ptr(gx), row_stride(gx), int(accumulate))
 
 
 class _PoolLocalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan, reduce):
-        x = _rows(x.detach(), "x")
+        x = _features(x.detach(), "x")
         T, Cc = x.shape
         out = torch.empty(T, Cc, dtype=torch.float32, device=x.device)
         argmax = torch.empty(plan.n_cells, Cc, dtype=torch.int32, device=x.device) if reduce == "max" else None
@@ -209,7 +174,7 @@ class _PoolLocalFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = _rows(g, "grad")
+        g = _features(g, "grad")
         gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
         _launch_pool_backward(g, 0, g.shape[1], ctx.plan, ctx.reduce, ctx.argmax, gx, False)
         return gx, None, None
@@ -218,7 +183,7 @@ class _PoolLocalFn(torch.autograd.Function):
 class _PoolCatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, plan, reduce):
-        net = _rows(net.detach(), "net")
+        net = _features(net.detach(), "net")
         T, Cc = net.shape
         cat = torch.empty(T, 2 * Cc, dtype=torch.float32, device=net.device)
         cat[:, :Cc].copy_(net)
@@ -229,7 +194,7 @@ class _PoolCatFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = _rows(g, "grad")
+        g = _features(g, "grad")
         Cc = ctx.C
         gx = g[:, :Cc].clone(memory_format=torch.contiguous_format)       # the left half's gradient; the pooled half's is added into it
         _launch_pool_backward(g, Cc, Cc, ctx.plan, ctx.reduce, ctx.argmax, gx, True)
@@ -239,13 +204,11 @@ class _PoolCatFn(torch.autograd.Function):
 class _PlaneMeanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c, plan):
-        c = _rows(c.detach(), "c")
+        c = _features(c.detach(), "c")
         T, Cc = c.shape
         plane = torch.empty(Cc, plan.n_cells, dtype=torch.float32, device=c.device)
-        L = _pool_lib()
-        with torch.cuda.device(c.device):
-            _ok(L.gh_plane_mean_forward(_ptr(c), c.stride(0) if T > 1 else Cc, T, Cc, plan.n_cells, _ptr(plan.cell_start),
-                                        _ptr(plan.order), _ptr(plane), _stream(c.device)), "gh_plane_mean_forward")
+        launch("gh_plane_mean_forward", c.device, ptr(c), row_stride(c), T, Cc, plan.n_cells, ptr(plan.cell_start), ptr(plan.order),
+               ptr(plane))
         ctx.plan, ctx.T = plan, T
         return plane
 
@@ -254,10 +217,7 @@ class _PlaneMeanFn(torch.autograd.Function):
         g = g.contiguous()
         Cc, plan = g.shape[0], ctx.plan
         gx = torch.empty(ctx.T, Cc, dtype=torch.float32, device=g.device)
-        L = _pool_lib()
-        with torch.cuda.device(g.device):
-            _ok(L.gh_plane_mean_backward(_ptr(g), ctx.T, Cc, plan.n_cells, _ptr(plan.cell_start), _ptr(plan.order), _ptr(gx), Cc,
-                                         _stream(g.device)), "gh_plane_mean_backward")
+        launch("gh_plane_mean_backward", g.device, ptr(g), ctx.T, Cc, plan.n_cells, ptr(plan.cell_start), ptr(plan.order), ptr(gx), Cc)
         return gx, None
 
 
@@ -280,7 +240,7 @@ def pool_local(x: torch.Tensor, plan: PoolPlan, reduce: str = "max", out: Option
         if not x.is_cuda:
             out.copy_(_pool_local_ref(x.detach(), plan, reduce))
             return out
-        xr = _rows(x.detach(), "x")
+        xr = _features(x.detach(), "x")
         argmax = torch.empty(plan.n_cells, x.shape[1], dtype=torch.int32, device=x.device) if reduce == "max" else None
         _launch_pool_forward(xr, plan, reduce, out, 0, argmax)
         return out
@@ -312,7 +272,7 @@ def pool_argmax(x: torch.Tensor, plan: PoolPlan) -> torch.Tensor:
     plan._fits(x, "x")
     if not x.is_cuda:
         return _cell_max(x.detach(), plan)[1]
-    xr = _rows(x.detach(), "x")
+    xr = _features(x.detach(), "x")
     out = torch.empty_like(xr, memory_format=torch.contiguous_format)
     argmax = torch.empty(plan.n_cells, x.shape[1], dtype=torch.int32, device=x.device)
     _launch_pool_forward(xr, plan, "max", out, 0, argmax)

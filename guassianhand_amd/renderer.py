@@ -19,6 +19,7 @@ from typing import Dict, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
+from ._call import launch, lib, ptr
 from .camera import pack_cameras_from_w2c
 from .rasterizer import rasterize_views
 
@@ -72,9 +73,6 @@ def gs_activations(raw: Dict[str, torch.Tensor], pts: torch.Tensor, *, use_rgb: 
 class _SelectRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, score, points, features, lo, hi):
-        import ctypes as C
-        from . import _abi, _lib
-        L = _lib.lib()
         dev = points.device
         if dev.type != "cuda":
             raise RuntimeError("select_gaussians needs tensors on a ROCm device (no CPU fallback)")
@@ -84,15 +82,9 @@ class _SelectRows(torch.autograd.Function):
         out = [torch.empty(N, 3, device=dev), torch.empty(N, Cf, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, Cf, device=dev)]
         idx = [torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)]
         counts = torch.empty(2, dtype=torch.int32, device=dev)
-        nws = L.gh_select_workspace_bytes(N)
-        ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = L.gh_select_rows(p(sc), N, float(lo), float(hi), p(pts), p(feat), Cf, p(out[0]), p(out[1]), p(out[2]), p(out[3]),
-                                  p(idx[0]), p(idx[1]), p(counts), p(ws), ws.numel(),
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gh_select_rows failed: {_abi.status_name(rc)}")
+        ws = torch.empty(max(lib().gh_select_workspace_bytes(N), 8), dtype=torch.uint8, device=dev)
+        launch("gh_select_rows", dev, ptr(sc), N, float(lo), float(hi), ptr(pts), ptr(feat), Cf, *[ptr(t) for t in out + idx],
+               ptr(counts), ptr(ws), ws.numel())
         nv, nc = counts.tolist()                                  # the one host read-back (the reference makes four)
         ctx.shape = (N, Cf)
         ctx.save_for_backward(idx[0][:nv], idx[1][:nc])

@@ -17,48 +17,37 @@ validity gate (`gs_valid`) and the position refinement (`vert_pos_refinement`) t
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
+_BASES = {"GS3DRenderer": ("tgs.models.renderer_one_shot", "fused_renderer_cls"),            # name -> (the base's module, its graft)
+          "GS3DRendererEdit": ("tgs.models.renderer_one_shot_edit", "fused_renderer_cls_edit")}
+_SUFFIXES = {"FusedHead": (False, True, "the fused Gaussian head"),                            # suffix -> (gate, head, doc)
+             "FusedGate": (True, False, "the fused gate and refinement"),
+             "FusedAll": (True, True, "the fused gate and refinement and Gaussian head")}
 
 
-def __getattr__(name):
-    if name == "GS3DRenderer":
-        if name not in _cache:
-            from tgs.models.renderer_one_shot import GS3DRenderer as base
-            from .renderer import fused_renderer_cls
-            _cache[name] = fused_renderer_cls(base)
-        return _cache[name]
-    if name == "GS3DRendererEdit":
-        if name not in _cache:
-            from tgs.models.renderer_one_shot_edit import GS3DRenderer as base
-            from .renderer import fused_renderer_cls_edit
-            _cache[name] = fused_renderer_cls_edit(base)
-        return _cache[name]
-    if name in ("GS3DRendererFusedHead", "GS3DRendererEditFusedHead"):
-        if name not in _cache:
-            base = __getattr__(name[:-len("FusedHead")])
+def _build(name):
+    if name in _BASES:
+        from importlib import import_module
+        from . import renderer
+        module, graft = _BASES[name]
+        return getattr(renderer, graft)(import_module(module).GS3DRenderer)
+    for suffix, (gate, head, doc) in _SUFFIXES.items():
+        if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
+            base = __getattr__(name[:-len(suffix)])
             from .gs_head import fuse_gs_head
+            from .vert_mlp import fuse_vert_mlps
 
             def configure(self, *args, **kwargs):
                 base.configure(self, *args, **kwargs)
-                fuse_gs_head(self)
-
-            _cache[name] = type(base.__name__, (base,), {"configure": configure, "__module__": __name__,
-                                                         "__doc__": f"{base.__doc__}, and the fused Gaussian head"})
-        return _cache[name]
-    for suffix, gate, head in (("FusedGate", True, False), ("FusedAll", True, True)):
-        if name in ("GS3DRenderer" + suffix, "GS3DRendererEdit" + suffix):
-            if name not in _cache:
-                base = __getattr__(name[:-len(suffix)])
-                from .gs_head import fuse_gs_head
-                from .vert_mlp import fuse_vert_mlps
-
-                def configure(self, *args, _base=base, _head=head, **kwargs):
-                    _base.configure(self, *args, **kwargs)
+                if gate:
                     fuse_vert_mlps(self)
-                    if _head:
-                        fuse_gs_head(self)
+                if head:
+                    fuse_gs_head(self)
 
-                _cache[name] = type(base.__name__, (base,), {"configure": configure, "__module__": __name__,
-                                                             "__doc__": f"{base.__doc__}, and the fused gate and refinement" +
-                                                                        (" and Gaussian head" if head else "")})
-            return _cache[name]
+            return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
     raise AttributeError(name)
+
+
+def __getattr__(name):
+    if name not in _cache:
+        _cache[name] = _build(name)
+    return _cache[name]

@@ -9,13 +9,13 @@ the fit-loop host logic — go through torch's grid_sample, which the GPU test c
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import _abi, _lib
+from . import _abi
+from ._call import launch, ptr
 
 
 def to_channel_last(param_chw: torch.Tensor) -> torch.Tensor:
@@ -29,17 +29,12 @@ def to_reference_layout(map_hwc: torch.Tensor) -> torch.Tensor:
 class _UvSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, map_hwc, uv):
-        L = _lib.lib()
         m = map_hwc.detach().float().contiguous()
         u = uv.detach().float().contiguous()
         Hm, Wm, Cc = m.shape
         P = u.shape[0]
         out = torch.empty(P, Cc, dtype=torch.float32, device=m.device)
-        with torch.cuda.device(m.device):
-            rc = L.gh_uv_sample_forward(C.c_void_p(m.data_ptr()), C.c_void_p(u.data_ptr()), C.c_void_p(out.data_ptr()), P, Cc,
-                                        Hm, Wm, C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"gh_uv_sample_forward failed: {_abi.status_name(rc)}")
+        launch("gh_uv_sample_forward", m.device, ptr(m), ptr(u), ptr(out), P, Cc, Hm, Wm)
         ctx.save_for_backward(u)
         ctx.shape = (Hm, Wm, Cc)
         return out
@@ -131,10 +126,6 @@ class ActiveTexels:
         return out.view(self.Hm, self.Wm, -1)
 
 
-def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _need_device(*ts: torch.Tensor) -> None:
     for t in ts:
         if not t.is_cuda:
@@ -146,14 +137,9 @@ def _need_device(*ts: torch.Tensor) -> None:
 def uv_gather(texels: torch.Tensor, at: ActiveTexels) -> torch.Tensor:
     """(U,C) active texels -> per-Gaussian values (P,C); no autograd (the fit loop calls uv_gather_backward itself)."""
     _need_device(texels, at.slot, at.w)
-    L = _lib.lib()
     Cc = texels.shape[1]
     out = torch.empty(at.P, Cc, dtype=torch.float32, device=texels.device)
-    with torch.cuda.device(texels.device):
-        rc = L.gh_uv_gather_forward(C.c_void_p(texels.data_ptr()), C.c_void_p(at.slot.data_ptr()), C.c_void_p(at.w.data_ptr()),
-                                    C.c_void_p(out.data_ptr()), at.P, Cc, _stream(texels))
-    if rc != 0:
-        raise RuntimeError(f"gh_uv_gather_forward failed: {_abi.status_name(rc)}")
+    launch("gh_uv_gather_forward", texels.device, ptr(texels), ptr(at.slot), ptr(at.w), ptr(out), at.P, Cc)
     return out
 
 
@@ -163,26 +149,16 @@ def uv_gather_backward(grad_out: torch.Tensor, at: ActiveTexels, grad_texels: to
     g = grad_out.detach().float().contiguous()
     _need_device(g, grad_texels, at.row_ptr, at.pairs, at.w)
     assert g.shape == (at.P, grad_texels.shape[1]) and grad_texels.shape[0] == at.U
-    L = _lib.lib()
-    with torch.cuda.device(g.device):
-        rc = L.gh_uv_scatter_sorted(C.c_void_p(at.row_ptr.data_ptr()), C.c_void_p(at.pairs.data_ptr()), C.c_void_p(at.w.data_ptr()),
-                                    C.c_void_p(g.data_ptr()), C.c_void_p(grad_texels.data_ptr()), at.U, g.shape[1], _stream(g))
-    if rc != 0:
-        raise RuntimeError(f"gh_uv_scatter_sorted failed: {_abi.status_name(rc)}")
+    launch("gh_uv_scatter_sorted", g.device, ptr(at.row_ptr), ptr(at.pairs), ptr(at.w), ptr(g), ptr(grad_texels), at.U, g.shape[1])
 
 
 def uv_gather2(texels_a: torch.Tensor, texels_b: torch.Tensor, at: ActiveTexels):
     """uv_gather of two maps that share the texel index, in one launch (gh_uv_gather_forward2): ((P,Ca), (P,Cb))."""
     _need_device(texels_a, texels_b, at.slot, at.w)
-    L = _lib.lib()
     Ca, Cb = texels_a.shape[1], texels_b.shape[1]
     oa = torch.empty(at.P, Ca, dtype=torch.float32, device=texels_a.device)
     ob = torch.empty(at.P, Cb, dtype=torch.float32, device=texels_a.device)
-    with torch.cuda.device(texels_a.device):
-        rc = L.gh_uv_gather_forward2(C.c_void_p(texels_a.data_ptr()), Ca, C.c_void_p(texels_b.data_ptr()), Cb, C.c_void_p(at.slot.data_ptr()),
-                                     C.c_void_p(at.w.data_ptr()), C.c_void_p(oa.data_ptr()), C.c_void_p(ob.data_ptr()), at.P, _stream(texels_a))
-    if rc != 0:
-        raise RuntimeError(f"gh_uv_gather_forward2 failed: {_abi.status_name(rc)}")
+    launch("gh_uv_gather_forward2", texels_a.device, ptr(texels_a), Ca, ptr(texels_b), Cb, ptr(at.slot), ptr(at.w), ptr(oa), ptr(ob), at.P)
     return oa, ob
 
 
@@ -195,13 +171,8 @@ def uv_gather_backward2(grad_a: torch.Tensor, grad_b: torch.Tensor, at: ActiveTe
     _need_device(ga, gb, grad_texels_a, grad_texels_b, at.row_ptr, at.pairs, at.w)
     assert ga.shape == (at.P, grad_texels_a.shape[1]) and gb.shape == (at.P, grad_texels_b.shape[1])
     assert grad_texels_a.shape[0] == at.U and grad_texels_b.shape[0] == at.U
-    L = _lib.lib()
-    with torch.cuda.device(ga.device):
-        rc = L.gh_uv_scatter_sorted2(C.c_void_p(at.row_ptr.data_ptr()), C.c_void_p(at.pairs.data_ptr()), C.c_void_p(at.w.data_ptr()),
-                                     C.c_void_p(ga.data_ptr()), ga.shape[1], C.c_void_p(grad_texels_a.data_ptr()),
-                                     C.c_void_p(gb.data_ptr()), gb.shape[1], C.c_void_p(grad_texels_b.data_ptr()), at.U, _stream(ga))
-    if rc != 0:
-        raise RuntimeError(f"gh_uv_scatter_sorted2 failed: {_abi.status_name(rc)}")
+    launch("gh_uv_scatter_sorted2", ga.device, ptr(at.row_ptr), ptr(at.pairs), ptr(at.w), ptr(ga), ga.shape[1], ptr(grad_texels_a),
+           ptr(gb), gb.shape[1], ptr(grad_texels_b), at.U)
 
 
 class AdamReg:
@@ -229,20 +200,14 @@ class AdamReg:
         grad: use this buffer (same shape, fp32, contiguous; it is cleared like `.grad`) instead of `.grad` — a gradient the
         kernels already wrote somewhere needs no copy. sums=False: do not reduce the block partials (see `sums()`)."""
         self.t += 1
-        L = _lib.lib()
         p = self.param
         g = self.grad if grad is None else grad
         if grad is not None:
             _need_device(g)
             assert g.numel() == p.numel()
-        with torch.cuda.device(p.device):
-            rc = L.gh_adam_reg_step(C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(self.exp_avg.data_ptr()),
-                                    C.c_void_p(self.exp_avg_sq.data_ptr()), p.numel(), self.t, self.lr, self.betas[0], self.betas[1],
-                                    self.eps, self.reg_l1, self.reg_l2, C.c_void_p(self.partials.data_ptr()), self.n_partials,
-                                    None if guard is None else C.c_void_p(guard.data_ptr()),
-                                    C.c_void_p(self.step_state.data_ptr()), _stream(p))
-        if rc != 0:
-            raise RuntimeError(f"gh_adam_reg_step failed: {_abi.status_name(rc)}")
+        launch("gh_adam_reg_step", p.device, ptr(p), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq), p.numel(), self.t, self.lr,
+               self.betas[0], self.betas[1], self.eps, self.reg_l1, self.reg_l2, ptr(self.partials), self.n_partials, ptr(guard),
+               ptr(self.step_state))
         return self.partials.sum(0) if sums else None
 
     def sums(self) -> torch.Tensor:
@@ -253,7 +218,6 @@ class AdamReg:
 def adam_group_step(adams, guard: Optional[torch.Tensor] = None, grads=None) -> None:
     """One launch for the step of up to four AdamReg states that share lr / betas / eps (gh_adam_reg_step_group): the same
     updates, moments, step counts and block partials as stepping them one by one. grads[i] (optional) replaces adams[i].grad."""
-    L = _lib.lib()
     a0 = adams[0]
     arr = (_abi.GhAdamTensor * len(adams))()
     for i, a in enumerate(adams):
@@ -264,25 +228,16 @@ def adam_group_step(adams, guard: Optional[torch.Tensor] = None, grads=None) -> 
         assert g.numel() == a.param.numel()
         arr[i] = _abi.GhAdamTensor(a.param.data_ptr(), g.data_ptr(), a.exp_avg.data_ptr(), a.exp_avg_sq.data_ptr(), a.param.numel(),
                                    a.reg_l1, a.reg_l2, a.partials.data_ptr(), a.n_partials, a.step_state.data_ptr())
-    with torch.cuda.device(a0.param.device):
-        rc = L.gh_adam_reg_step_group(arr, len(adams), a0.t, a0.lr, a0.betas[0], a0.betas[1], a0.eps,
-                                      None if guard is None else C.c_void_p(guard.data_ptr()), _stream(a0.param))
-    if rc != 0:
-        raise RuntimeError(f"gh_adam_reg_step_group failed: {_abi.status_name(rc)}")
+    launch("gh_adam_reg_step_group", a0.param.device, arr, len(adams), a0.t, a0.lr, a0.betas[0], a0.betas[1], a0.eps, ptr(guard))
 
 
 def reg_total(a: AdamReg, col_a: int, k_a: float, b: AdamReg, col_b: int, k_b: float, base: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(base + reg, reg) with reg = k_a * sums(a)[col_a] + k_b * sums(b)[col_b] of the last steps' block partials, as one
     2-element device tensor from one small kernel (gh_reg_total)."""
-    L = _lib.lib()
     out = torch.empty(2, dtype=torch.float32, device=a.param.device)
     if base is not None:
         base = base.detach().reshape(1)
         _need_device(base)
-    with torch.cuda.device(out.device):
-        rc = L.gh_reg_total(C.c_void_p(a.partials.data_ptr()), a.n_partials, int(col_a), float(k_a), C.c_void_p(b.partials.data_ptr()),
-                            b.n_partials, int(col_b), float(k_b), None if base is None else C.c_void_p(base.data_ptr()),
-                            C.c_void_p(out.data_ptr()), _stream(out))
-    if rc != 0:
-        raise RuntimeError(f"gh_reg_total failed: {_abi.status_name(rc)}")
+    launch("gh_reg_total", out.device, ptr(a.partials), a.n_partials, int(col_a), float(k_a), ptr(b.partials), b.n_partials, int(col_b),
+           float(k_b), ptr(base), ptr(out))
     return out

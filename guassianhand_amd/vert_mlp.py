@@ -33,34 +33,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi, _lib
+from . import _abi
+from ._call import check_f32, launch, lib, ptr, row_stride, rows, struct, workspace
 
 PARAMS = _abi.VERT_PARAMS                                        # the order of `params` (GhVertParams)
 ACTS = {"sigmoid": _abi.GH_VERT_ACT_SIGMOID, "tanh_offset": _abi.GH_VERT_ACT_TANH_OFFSET}
 MAX_CF = _abi.GH_VERT_MAX_CF
-_declared = False
-
-
-def _vert_lib() -> C.CDLL:
-    global _declared
-    L = _lib.lib()
-    if not _declared:
-        _abi.declare_vert(L)
-        _declared = True
-    return L
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ok(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {_abi.status_name(rc)}")
 
 
 def param_shapes(Cf: int, K: int):
@@ -76,16 +54,8 @@ def _check(x, pts, params, act, eps) -> int:
     params = tuple(params)
     if len(params) != len(PARAMS):
         raise ValueError(f"params: expected the {len(PARAMS)} tensors {PARAMS}, got {len(params)}")
-    for name, t, nd in (("x", x, 2), ("pts", pts, 2)) + tuple((n, p, 2 if n.endswith("weight") and not n.startswith("ln") else 1)
-                                                              for n, p in zip(PARAMS, params)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name}: expected float32, got {t.dtype}")
-        if t.dim() != nd:
-            raise ValueError(f"{name}: expected {nd} dimensions, got {tuple(t.shape)}")
-        if t.device != x.device:
-            raise ValueError(f"{name} is on {t.device}, x on {x.device}")
+    check_f32(x, (("x", x, 2), ("pts", pts, 2)) + tuple((n, p, 2 if n.endswith("weight") and not n.startswith("ln") else 1)
+                                                        for n, p in zip(PARAMS, params)))
     Cf = x.shape[1]
     if not 1 <= Cf <= MAX_CF:
         raise ValueError(f"x has {Cf} columns: the block takes 1 to {MAX_CF} features")
@@ -122,37 +92,21 @@ def _vert_block_ref(x, pts, params, *, act="sigmoid", radius=0.001, eps=1e-6, ac
 
 
 # ---- device path ---------------------------------------------------------------------------------------------------------------
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """A (P,C) float32 tensor the kernels read in place: unit column stride, any row stride >= C; anything else is copied once."""
-    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _row_stride(t: torch.Tensor) -> int:
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
-def _struct(cls, tensors):
-    return cls(*[None if t is None else t.data_ptr() for t in tensors])
-
-
 class _VertBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pts, cfg, *params):
         act, radius, eps = cfg
         ctx.set_materialize_grads(False)
-        x, pts = _rows(x.detach()), pts.detach().contiguous()
+        x, pts = rows(x.detach()), pts.detach().contiguous()
         params = [p.detach().contiguous() for p in params]
         P, Cf = x.shape
         K, dev = params[6].shape[0], x.device
         out = torch.empty(P, K, dtype=torch.float32, device=dev)
         if P > 0:
             desc = _abi.GhVertDesc(K, ACTS[act], float(radius), float(eps))
-            pstruct = _struct(_abi.GhVertParams, params)
-            with torch.cuda.device(dev):
-                _ok(_vert_lib().gh_vert_forward(_ptr(x), _row_stride(x), _ptr(pts), P, Cf, C.byref(pstruct), C.byref(desc), _ptr(out),
-                                                _stream(dev)), f"gh_vert_forward (P={P}, Cf={Cf}, K={K})")
+            pstruct = struct(_abi.GhVertParams, params)
+            launch("gh_vert_forward", dev, ptr(x), row_stride(x), ptr(pts), P, Cf, C.byref(pstruct), C.byref(desc), ptr(out),
+                   what=f"gh_vert_forward (P={P}, Cf={Cf}, K={K})")
         ctx.cfg = cfg
         ctx.save_for_backward(x, pts, *params)
         return out
@@ -176,16 +130,13 @@ class _VertBlockFn(torch.autograd.Function):
                     g.zero_()
         else:
             g = None if g_out is None else g_out.float().contiguous()
-            L = _vert_lib()
-            nbytes = int(L.gh_vert_workspace_bytes(P, D, Hd, K)) if need_w else 0
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if need_w else None
+            nbytes = int(lib().gh_vert_workspace_bytes(P, D, Hd, K)) if need_w else 0
+            ws = workspace(nbytes, dev) if need_w else None
             desc = _abi.GhVertDesc(K, ACTS[act], float(radius), float(eps))
-            pstruct = _struct(_abi.GhVertParams, params)
-            gstruct = _struct(_abi.GhVertGrads, gparams) if need_w else None
-            with torch.cuda.device(dev):
-                _ok(L.gh_vert_backward(_ptr(x), _row_stride(x), _ptr(pts), P, Cf, C.byref(pstruct), C.byref(desc), _ptr(g), _ptr(gx), Cf,
-                                       _ptr(gpts), C.byref(gstruct) if need_w else None, _ptr(ws), nbytes, _stream(dev)),
-                    f"gh_vert_backward (P={P}, Cf={Cf}, K={K})")
+            pstruct = struct(_abi.GhVertParams, params)
+            gstruct = struct(_abi.GhVertGrads, gparams) if need_w else None
+            launch("gh_vert_backward", dev, ptr(x), row_stride(x), ptr(pts), P, Cf, C.byref(pstruct), C.byref(desc), ptr(g), ptr(gx), Cf,
+                   ptr(gpts), C.byref(gstruct) if need_w else None, ptr(ws), nbytes, what=f"gh_vert_backward (P={P}, Cf={Cf}, K={K})")
         gp = [g if need else None for g, need in zip(gparams, ctx.needs_input_grad[3:])] if need_w else [None] * len(params)
         return (gx if ctx.needs_input_grad[0] else None, gpts, None, *gp)
 

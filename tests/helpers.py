@@ -1,8 +1,17 @@
 """Shared helpers for the parity tests (oracle = checker, HIP path = thing under test)."""
 import math
+import os
+import re
+
 import torch
 
 from guassianhand_amd.scenes import make_scene
+
+
+def header_symbols(header_file_name):
+    """The sorted names of the functions that include/<header_file_name> declares."""
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", header_file_name)).read()
+    return sorted(set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", txt, flags=re.M)))
 
 
 class GoldenNpz:

@@ -7,25 +7,30 @@ import re
 import pytest
 
 from guassianhand_amd import _abi
+from tests.helpers import header_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "gh_raster.h")).read()
-    return sorted(set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", txt, flags=re.M)))
-
-
 def test_header_declares_expected_symbols():
-    assert header_symbols() == sorted(_abi.EXPORTED_SYMBOLS)
+    assert header_symbols("gh_raster.h") == sorted(_abi.EXPORTED_SYMBOLS)
 
 
 def test_library_exports_every_declared_symbol(gh_lib_path):
     L = C.CDLL(gh_lib_path)
-    for sym in header_symbols():
+    for sym in header_symbols("gh_raster.h"):
         assert hasattr(L, sym), sym
     _abi.declare(L)
     assert L.gh_version() == (0 << 16) | 8
+
+
+def test_declare_covers_every_symbol_of_every_header(gh_lib_path):
+    """_abi.declare is the one attachment _lib.lib() makes: no block declares its own header before its first call."""
+    L = C.CDLL(gh_lib_path)
+    _abi.declare(L)
+    assert len(set(_abi.ALL_SYMBOLS)) == len(_abi.ALL_SYMBOLS)
+    for sym in _abi.ALL_SYMBOLS:
+        assert getattr(L, sym).argtypes is not None, sym
 
 
 def test_struct_sizes_match_header():

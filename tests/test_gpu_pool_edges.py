@@ -16,7 +16,7 @@ holds one) the kernel must return the same NaN / infinity."""
 import pytest
 import torch
 
-from guassianhand_amd import _abi, pool
+from guassianhand_amd import _abi, _call, pool
 from guassianhand_amd.pool import LocalPoolPointnet, PoolPlan, plane_mean, pool_cat, pool_local, scatter_max, scatter_mean
 from tests.pool_helpers import (NAN_VALUES, SWEEP, U, assert_within, assert_within_or_same_nonfinite, case_id, fixture_cfg,
                                 fixture_weights, load_fixture, loop_pool, permute_within_cells, plane_bounds, pool_bounds, sweep_case)
@@ -229,8 +229,8 @@ def test_raw_entry_points_with_column_offsets_and_strided_gradients(case):
     """What the Python wrappers never pass: out_col > 0 on the base pointer of the (T, 2C) buffer, accumulate = 1 into a grad_x of
     row stride 2C, x_stride > C for the plane. Bit-equal to the view-pointer forms."""
     s, plan = _on_device(case)
-    L, T, Cc, n = pool._pool_lib(), s.T, s.C, s.n
-    ptr, stream = pool._ptr, pool._stream(DEV)
+    L, T, Cc, n = _call.lib(), s.T, s.C, s.n
+    ptr, stream = _call.ptr, _call.stream(DEV)
     xd = s.x.to(DEV)
     G = torch.cat([s.left, s.cot], dim=1).to(DEV).contiguous()
     for kind in KINDS:

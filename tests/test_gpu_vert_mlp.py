@@ -206,18 +206,17 @@ def test_frozen_backward_is_the_same_grad_x_and_no_parameter_gradients(dev, p257
 
 def test_null_cotangent_writes_zeros(dev, p257):
     """gh_vert_backward with g_out = NULL: every gradient is written, as zero, frozen and trainable."""
-    from guassianhand_amd import _abi
-    from guassianhand_amd import vert_mlp as V
+    from guassianhand_amd import _abi, _call
     inputs, _, _ = p257
     x, pts, params = inputs[0], inputs[1], inputs[2:]
-    L = V._vert_lib()
+    L = _call.lib()
     desc = _abi.GhVertDesc(3, _abi.GH_VERT_ACT_TANH_OFFSET, 0.001, 1e-6)
-    ps = V._struct(_abi.GhVertParams, params)
-    ptr, stream = V._ptr, V._stream(dev)
+    ps = _call.struct(_abi.GhVertParams, params)
+    ptr, stream = _call.ptr, _call.stream(dev)
     for trainable in (False, True):
         gx, gp = torch.full_like(x, 7.0), torch.full_like(pts, 7.0)
         grads = [torch.full_like(p, 7.0) for p in params]
-        gs = V._struct(_abi.GhVertGrads, grads)
+        gs = _call.struct(_abi.GhVertGrads, grads)
         n = int(L.gh_vert_workspace_bytes(257, 134, 33, 3))
         ws = torch.empty(n, dtype=torch.uint8, device=dev)
         rc = L.gh_vert_backward(ptr(x), 131, ptr(pts), 257, 131, C.byref(ps), C.byref(desc), None, ptr(gx), 131, ptr(gp),

@@ -11,6 +11,7 @@ import torch
 
 from guassianhand_amd import _abi
 from guassianhand_amd import gs_head as H
+from tests.helpers import header_symbols
 
 FIELDS = ("xyz", "scaling", "rotation", "opacity", "shs")
 
@@ -156,19 +157,12 @@ def test_library_exports_the_head_symbols(gh_lib_path):
     for sym in _abi.HEAD_SYMBOLS:
         assert hasattr(L, sym), sym
     _abi.declare_head(L)
-    assert sorted(_abi.HEAD_SYMBOLS) == sorted(_header_symbols())
+    assert sorted(_abi.HEAD_SYMBOLS) == header_symbols("gh_head.h")
     nb = -(-98562 // _abi.GH_HEAD_ROWS)
     assert L.gh_head_workspace_bytes(98562, 128, 14) >= 4 * nb * 14 * (128 + 1)
     assert L.gh_head_workspace_bytes(1, 3, 59) > 0
     for P, Cin, O in ((0, 128, 14), (-1, 128, 14), (10, 0, 14), (10, 128, 13), (10, 128, 15), (10, 128, 60), (10, 128, 11), (10, 128, 0)):
         assert L.gh_head_workspace_bytes(P, Cin, O) == 0, (P, Cin, O)
-
-
-def _header_symbols():
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = open(os.path.join(root, "include", "gh_head.h")).read()
-    return set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", txt, flags=re.M))
 
 
 def test_c_abi_refuses_bad_arguments_before_any_launch(gh_lib_path):

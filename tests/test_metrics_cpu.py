@@ -11,6 +11,7 @@ import torch
 
 from guassianhand_amd import _abi
 from guassianhand_amd.metrics import Evaluator, image_scores
+from tests.helpers import header_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -209,13 +210,8 @@ def test_skimage_agrees_if_installed():
 
 
 # ---- C-ABI (include/gh_metrics.h) -----------------------------------------------------------------------------------------------
-def _metrics_header_symbols():
-    txt = open(os.path.join(ROOT, "include", "gh_metrics.h")).read()
-    return sorted(set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", txt, flags=re.M)))
-
-
 def test_metrics_header_declares_the_metrics_symbols():
-    assert _metrics_header_symbols() == sorted(_abi.METRICS_SYMBOLS)
+    assert header_symbols("gh_metrics.h") == sorted(_abi.METRICS_SYMBOLS)
     assert not set(_abi.METRICS_SYMBOLS) & set(_abi.EXPORTED_SYMBOLS)
     h = open(os.path.join(ROOT, "include", "gh_metrics.h")).read()
     for name in ("GH_METRICS_CHW", "GH_METRICS_PRED_HWC", "GH_METRICS_GT_HWC"):

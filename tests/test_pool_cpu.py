@@ -12,6 +12,7 @@ import torch
 
 from guassianhand_amd import _abi, pool
 from guassianhand_amd.pool import LocalPoolPointnet, PoolPlan, plane_mean, pool_cat, pool_local, scatter_max, scatter_mean
+from tests.helpers import header_symbols
 from tests.pool_helpers import U, assert_within, fixture_cfg, fixture_weights, load_fixture, rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -232,8 +233,7 @@ def test_encoder_has_the_reference_state_dict_keys(fx):
 # ---- C-ABI (include/gh_pool.h) ----------------------------------------------------------------------------------------------------
 def test_pool_header_mirror_and_library_agree(gh_lib_path):
     h = open(os.path.join(ROOT, "include", "gh_pool.h")).read()
-    syms = sorted(set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", h, flags=re.M)))
-    assert syms == sorted(_abi.POOL_SYMBOLS)
+    assert header_symbols("gh_pool.h") == sorted(_abi.POOL_SYMBOLS)
     assert not set(_abi.POOL_SYMBOLS) & (set(_abi.EXPORTED_SYMBOLS) | set(_abi.METRICS_SYMBOLS))
     for name in ("GH_POOL_MAX", "GH_POOL_MEAN", "GH_POOL_MAX_CELLS"):
         assert getattr(_abi, name) == int(re.search(rf"#define {name} (\d+)", h).group(1)), name

@@ -5,7 +5,6 @@ opt-in renderer names. No GPU compute is launched here."""
 import ctypes as C
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 
 from guassianhand_amd import _abi
 from guassianhand_amd import vert_mlp as V
+from tests.helpers import header_symbols
 
 KEYS = {"ln_weight": "ff.layer_norm.weight", "ln_bias": "ff.layer_norm.bias", "fc1_weight": "ff.fc1.weight", "fc1_bias": "ff.fc1.bias",
         "fc2_weight": "ff.fc2.weight", "fc2_bias": "ff.fc2.bias", "fc_weight": "fc.weight", "fc_bias": "fc.bias"}
@@ -121,18 +121,12 @@ def test_refinement_position_term_carries_no_gradient(fx):
     assert float(p.grad.abs().max()) < 0.1                         # (an identity term would add 1)
 
 
-def _header_symbols():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = open(os.path.join(root, "include", "gh_vert.h")).read()
-    return set(re.findall(r"^\s*(?:int|size_t)\s+(gh_\w+)\s*\(", txt, flags=re.M))
-
-
 def test_library_exports_the_vert_symbols(gh_lib_path):
     L = C.CDLL(gh_lib_path)
     for sym in _abi.VERT_SYMBOLS:
         assert hasattr(L, sym), sym
     _abi.declare_vert(L)
-    assert sorted(_abi.VERT_SYMBOLS) == sorted(_header_symbols())
+    assert sorted(_abi.VERT_SYMBOLS) == header_symbols("gh_vert.h")
     per_tile = 2 * 134 + 33 * 134 + 33 + 33 * 33 + 33 + 3 * 33 + 3
     assert L.gh_vert_workspace_bytes(98562, 134, 33, 3) >= 4 * -(-98562 // _abi.GH_VERT_ROWS) * per_tile
     assert L.gh_vert_workspace_bytes(1, 4, 1, 1) > 0 and L.gh_vert_workspace_bytes(1, 259, 64, 3) > 0
