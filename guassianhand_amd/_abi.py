@@ -292,10 +292,29 @@ def declare_vert(lib: C.CDLL) -> None:
                                      C.c_void_p]
 
 
-ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS
+# ---- include/gh_plane.h: the plane fetch (a header of its own, as gh_vert.h is) ----
+PLANE_SYMBOLS = ("gh_plane_workspace", "gh_plane_sample_forward", "gh_plane_index", "gh_plane_sample_backward")
+
+
+def declare_plane(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_plane.h declares."""
+    lib.gh_plane_workspace.restype = C.c_size_t
+    lib.gh_plane_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.gh_plane_sample_forward.restype = C.c_int
+    lib.gh_plane_sample_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]
+    lib.gh_plane_index.restype = C.c_int
+    lib.gh_plane_index.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]
+    lib.gh_plane_sample_backward.restype = C.c_int
+    lib.gh_plane_sample_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p]
+
+
+ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the five headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert):
+    """Attach argtypes/restypes for every symbol of the six headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane):
         one(lib)

@@ -14,14 +14,21 @@ validity gate (`gs_valid`) and the position refinement (`vert_pos_refinement`) t
 (include/gh_vert.h) while their dropout is inactive (eval mode); in train mode they keep the reference's torch forward.
 `GS3DRendererFusedAll` / `GS3DRendererEditFusedAll`: gate, refinement and head. All opt-in.
 
+`GS3DRendererFusedFetch` / `GS3DRendererEditFusedFetch`: `configure()` additionally calls `plane.fuse_plane_fetch(self)` — `forward`'s
+`query_triplane_texture` (the texture code sampled at every point's UV) then runs the plane fetch (include/gh_plane.h), whose
+gradient of the code is summed in a fixed order. `GS3DRendererFusedAllFetch` / `GS3DRendererEditFusedAllFetch`: gate, refinement,
+head and fetch. Opt-in as well: every name above keeps its behaviour.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
 _BASES = {"GS3DRenderer": ("tgs.models.renderer_one_shot", "fused_renderer_cls"),            # name -> (the base's module, its graft)
           "GS3DRendererEdit": ("tgs.models.renderer_one_shot_edit", "fused_renderer_cls_edit")}
-_SUFFIXES = {"FusedHead": (False, True, "the fused Gaussian head"),                            # suffix -> (gate, head, doc)
-             "FusedGate": (True, False, "the fused gate and refinement"),
-             "FusedAll": (True, True, "the fused gate and refinement and Gaussian head")}
+_SUFFIXES = {"FusedHead": (False, True, False, "the fused Gaussian head"),                     # suffix -> (gate, head, fetch, doc)
+             "FusedGate": (True, False, False, "the fused gate and refinement"),
+             "FusedAll": (True, True, False, "the fused gate and refinement and Gaussian head"),
+             "FusedFetch": (False, False, True, "the plane fetch"),
+             "FusedAllFetch": (True, True, True, "the fused gate and refinement, Gaussian head and plane fetch")}
 
 
 def _build(name):
@@ -30,10 +37,11 @@ def _build(name):
         from . import renderer
         module, graft = _BASES[name]
         return getattr(renderer, graft)(import_module(module).GS3DRenderer)
-    for suffix, (gate, head, doc) in _SUFFIXES.items():
+    for suffix, (gate, head, fetch, doc) in _SUFFIXES.items():
         if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
             base = __getattr__(name[:-len(suffix)])
             from .gs_head import fuse_gs_head
+            from .plane import fuse_plane_fetch
             from .vert_mlp import fuse_vert_mlps
 
             def configure(self, *args, **kwargs):
@@ -42,6 +50,8 @@ def _build(name):
                     fuse_vert_mlps(self)
                 if head:
                     fuse_gs_head(self)
+                if fetch:
+                    fuse_plane_fetch(self)
 
             return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
     raise AttributeError(name)
