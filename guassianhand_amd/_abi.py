@@ -311,10 +311,39 @@ def declare_plane(lib: C.CDLL) -> None:
                                              C.c_void_p]
 
 
-ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS
+# ---- include/gh_attn.h: the interaction attention's core (a header of its own, as gh_plane.h is) ----
+GH_ATTN_D = 32
+GH_ATTN_MAX_BH = 65535
+GH_ATTN_MAX_V = 1 << 30
+
+ATTN_SYMBOLS = ("gh_attn_workspace_bytes", "gh_attn_forward", "gh_attn_backward")
+
+
+class GhAttnDims(C.Structure):
+    _fields_ = [("BS", C.c_int32), ("V", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("norm", C.c_float)]
+
+
+class GhAttnTensor(C.Structure):
+    """A (BS, V, H, D) view with unit last stride: the pointer and the batch, row and head strides in elements."""
+    _fields_ = [("p", C.c_void_p), ("stride_b", C.c_int64), ("stride_v", C.c_int64), ("stride_h", C.c_int64)]
+
+
+def declare_attn(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_attn.h declares."""
+    T = C.POINTER(GhAttnTensor)
+    lib.gh_attn_workspace_bytes.restype = C.c_size_t
+    lib.gh_attn_workspace_bytes.argtypes = [C.POINTER(GhAttnDims)]
+    lib.gh_attn_forward.restype = C.c_int
+    lib.gh_attn_forward.argtypes = [C.POINTER(GhAttnDims), T, T, T, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gh_attn_backward.restype = C.c_int
+    lib.gh_attn_backward.argtypes = [C.POINTER(GhAttnDims), T, T, T, C.c_void_p, C.c_void_p, T] + [C.c_void_p] * 3 + \
+        [C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the six headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane):
+    """Attach argtypes/restypes for every symbol of the seven headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn):
         one(lib)

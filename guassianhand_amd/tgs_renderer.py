@@ -19,16 +19,23 @@ validity gate (`gs_valid`) and the position refinement (`vert_pos_refinement`) t
 gradient of the code is summed in a fixed order. `GS3DRendererFusedAllFetch` / `GS3DRendererEditFusedAllFetch`: gate, refinement,
 head and fetch. Opt-in as well: every name above keeps its behaviour.
 
+`GS3DRendererFusedAttn` / `GS3DRendererEditFusedAttn`: `configure()` additionally calls `attention.fuse_self_attn(self)` — the
+attention core of `self_attn_layer`, which `forward` applies to the points `mink_idxs_inter` flags, then runs the streaming-softmax
+kernels (include/gh_attn.h) while its dropout is inactive (eval mode); in train mode it keeps the reference's torch statements.
+`GS3DRendererFusedAllFetchAttn` / `GS3DRendererEditFusedAllFetchAttn`: gate, refinement, head, fetch and attention. Opt-in too.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
 _BASES = {"GS3DRenderer": ("tgs.models.renderer_one_shot", "fused_renderer_cls"),            # name -> (the base's module, its graft)
           "GS3DRendererEdit": ("tgs.models.renderer_one_shot_edit", "fused_renderer_cls_edit")}
-_SUFFIXES = {"FusedHead": (False, True, False, "the fused Gaussian head"),                     # suffix -> (gate, head, fetch, doc)
-             "FusedGate": (True, False, False, "the fused gate and refinement"),
-             "FusedAll": (True, True, False, "the fused gate and refinement and Gaussian head"),
-             "FusedFetch": (False, False, True, "the plane fetch"),
-             "FusedAllFetch": (True, True, True, "the fused gate and refinement, Gaussian head and plane fetch")}
+_SUFFIXES = {"FusedHead": (False, True, False, False, "the fused Gaussian head"),              # suffix -> (gate, head, fetch, attn, doc)
+             "FusedGate": (True, False, False, False, "the fused gate and refinement"),
+             "FusedAll": (True, True, False, False, "the fused gate and refinement and Gaussian head"),
+             "FusedFetch": (False, False, True, False, "the plane fetch"),
+             "FusedAllFetch": (True, True, True, False, "the fused gate and refinement, Gaussian head and plane fetch"),
+             "FusedAttn": (False, False, False, True, "the HIP attention core"),
+             "FusedAllFetchAttn": (True, True, True, True, "the fused gate and refinement, Gaussian head, plane fetch and HIP attention core")}
 
 
 def _build(name):
@@ -37,9 +44,10 @@ def _build(name):
         from . import renderer
         module, graft = _BASES[name]
         return getattr(renderer, graft)(import_module(module).GS3DRenderer)
-    for suffix, (gate, head, fetch, doc) in _SUFFIXES.items():
+    for suffix, (gate, head, fetch, attn, doc) in _SUFFIXES.items():
         if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
             base = __getattr__(name[:-len(suffix)])
+            from .attention import fuse_self_attn
             from .gs_head import fuse_gs_head
             from .plane import fuse_plane_fetch
             from .vert_mlp import fuse_vert_mlps
@@ -52,6 +60,8 @@ def _build(name):
                     fuse_gs_head(self)
                 if fetch:
                     fuse_plane_fetch(self)
+                if attn:
+                    fuse_self_attn(self)
 
             return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
     raise AttributeError(name)
