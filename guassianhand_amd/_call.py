@@ -1,5 +1,5 @@
 """What the Python wrappers of the C-ABI share: the loaded library, the ctypes forms of tensors and streams, the rows-in-place rule,
-the host-side argument check and the one way an entry point is called. rasterizer.py keeps wrappers of its own (its pointers are plain
+the host-side argument check and the one way an entry point is called. _raster_launch.py keeps wrappers of its own (its pointers are plain
 integers for struct fields, and its stream and device handling were tuned for the render loop)."""
 from __future__ import annotations
 

@@ -34,6 +34,7 @@ import torch.nn.functional as F
 
 from . import _abi
 from . import dist as ghdist
+from . import rasterizer as R
 from .renderer import GaussianModel
 from .uvmap import (ActiveTexels, AdamReg, adam_group_step, reg_total, to_reference_layout, uv_gather, uv_gather2,
                     uv_gather_backward, uv_gather_backward2, uv_sample)
@@ -91,11 +92,9 @@ class OneShotFit(nn.Module):
         if occlusion_bound:
             if static_geometry:
                 raise ValueError("OneShotFit: static_geometry (frozen Gaussians) or occlusion_bound (moving Gaussians), not both")
-            from .rasterizer import DepthBoundCache
-            self._geom_cache = DepthBoundCache()      # (ignored by calls of fewer than four 512x334 views' worth of pixels)
+            self._geom_cache = R.DepthBoundCache()      # (ignored by calls of fewer than four 512x334 views' worth of pixels)
         elif (static_geometry if static_geometry is not None else (render_fn is None and gs.xyz.is_cuda)):
-            from .rasterizer import GeometryCache
-            self._geom_cache = GeometryCache()
+            self._geom_cache = R.GeometryCache()
         self.keep_boundary_grads, self.boundary_grads, self.last_reg = False, None, None
         self._side = None
         if render_fn is None:
@@ -192,8 +191,7 @@ class OneShotFit(nn.Module):
         if gs.xyz.shape != self.gs.xyz.shape:
             raise ValueError("update_gaussians: the number of Gaussians is fixed (the UV lookup is indexed by it)")
         self.gs = GaussianModel(*[t.detach() for t in gs])
-        from .rasterizer import DepthBoundCache
-        if not isinstance(self._geom_cache, DepthBoundCache):      # (an occlusion bound survives a small move: that is its purpose)
+        if not isinstance(self._geom_cache, R.DepthBoundCache):      # (an occlusion bound survives a small move: that is its purpose)
             self.invalidate_geometry()
 
     skipped_steps = 0      # sync-free steps a miss of the speculative occlusion bound turned into no-ops (counted by step())
@@ -214,7 +212,6 @@ class OneShotFit(nn.Module):
                               sh_degree=self.sh_degree, sync=sync, **kw)
 
     def _is_depth_bound_cache(self) -> bool:
-        from . import rasterizer as R
         return isinstance(self._geom_cache, R.DepthBoundCache)
 
     # -- one optimisation step over all cameras (sharded over ranks) ------------------------------------
@@ -232,7 +229,6 @@ class OneShotFit(nn.Module):
             # there — the device-side guard turned that step into a no-op (NaN loss, untouched parameters) and the cache dropped the
             # bound. Look at the read-backs that have arrived, count the skipped step instead of leaving it unseen until somebody
             # calls check_overflow(), and go on: this step renders without a bound. Any other verdict (capacity, stale lists) raises.
-            from . import rasterizer as R
             try:
                 R.check_overflow(block=False)
             except R.GhDepthBoundMiss:
@@ -272,7 +268,6 @@ class OneShotFit(nn.Module):
             if out is None:
                 pass
             elif "image_chw" in out and out["image_chw"].is_cuda:    # fused loss + gradients on the rasteriser's layouts
-                from . import rasterizer as R
                 from .loss import fit_image_loss
                 loss_img = fit_image_loss(out["image_chw"], out["alpha"], sel(gt_rgb), sel(gt_mask),
                                           None if bbox_mask is None else sel(bbox_mask).float(), scale=1.0 / n_total,
@@ -292,7 +287,6 @@ class OneShotFit(nn.Module):
         # gradients. In a sharded fit the flag is summed with the gradients, so that every rank skips the same Adam step.
         local_guard = None
         if self._default_render and self.color_w.is_cuda and mine:
-            from . import rasterizer as R
             local_guard = R.last_guard()
         ovf = None
         if world > 1 and self.color_w.is_cuda:
@@ -300,7 +294,6 @@ class OneShotFit(nn.Module):
                 (local_guard.view(torch.int32)[1] & _abi.GH_COUNTER_ERROR_MASK).ne(0).float()      # bit 4 is information
         blk = None
         if use_block:
-            from . import rasterizer as R
             blk = R.last_grad_block()
             if not all(grads[k].data_ptr() == blk[0].data_ptr() + 4 * a for k, _, a, _ in blk[2] if k in grads):
                 raise RuntimeError("sharded fit: the blend gradients are not views of the rasteriser's gradient block")
@@ -390,7 +383,6 @@ class CapturedFitStep:
         self.fit, self.args = fit, args
         self.graph, self.loss, self.lr = None, None, None
         fit.step(*args, sync=True)                                   # sizes the instance capacity (a regular step)
-        from . import rasterizer as R
         R.check_overflow()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -403,7 +395,6 @@ class CapturedFitStep:
         return self.fit.lr0 * 0.5 ** sum(1 for m in MILESTONES if m <= self.fit.epoch)
 
     def _capture(self) -> None:
-        from . import rasterizer as R
         R.set_graph_mode(True)
         try:
             self.graph = torch.cuda.CUDAGraph()
@@ -429,7 +420,6 @@ class CapturedFitStep:
             # not a fault — but not what the fit holds now). This step runs as a regular one (it rebuilds the lists), then capture again.
             # (Checked BEFORE the learning rate: a capture over an empty cache records the BUILD — a full forward — and every replay
             # of that graph would rebuild the lists instead of refreshing them; found by tools/fuzz_fit.py.)
-            from . import rasterizer as R
             loss = self.fit.step(*self.args, sync=True).detach().clone()   # THIS replay's step, run eagerly (at the current learning rate)
             R.check_overflow()
             self._capture()
@@ -441,7 +431,6 @@ class CapturedFitStep:
 
     def check(self) -> None:
         """Host read-back of the captured render's counters: raises rasterizer.GhOverflowError if a replay overflowed."""
-        from . import rasterizer as R
         for counters, cap, key, full in self.counters:
             w = R.counter_word(counters.tolist())
             # stale static lists (an opacity above their bound) / GH_FLAG_DEPTH24 not holding / an instance overflow: the rasteriser

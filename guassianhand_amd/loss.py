@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import torch
 
+from . import rasterizer as R
 from ._call import launch, ptr
 
 _N_PARTIALS = 1024
@@ -96,7 +97,6 @@ class _RenderedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, cams, *gaussians):
-        from . import rasterizer as R
         spec = a.spec
         if spec[0] == "l1":                          # the fused epilogue reads the target as it lies: float32, contiguous, image-shaped
             tgt = spec[1].detach().float().contiguous()
@@ -121,13 +121,11 @@ class _RenderedLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _gi, _ga, _gr):
-        from . import rasterizer as R
         return R._views_backward(ctx, ctx.dimg, ctx.dal, g_loss)
 
 
 def _rendered_loss(spec, cams, xyz, opacity, scaling, rotation, shs, **kw):
     """kw: rasterize_views' keywords (but return_alpha: the fit form renders alpha) and defer_loss."""
-    from . import rasterizer as R
     return R._apply_views(_RenderedLoss, cams, xyz, opacity, scaling, rotation, shs, return_alpha=spec[0] == "fit", spec=spec, **kw)
 
 

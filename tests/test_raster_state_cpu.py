@@ -1,4 +1,4 @@
-"""The rasteriser's host state (guassianhand_amd/rasterizer.py, round 5): one _DeviceState per device behind a re-entrant lock,
+"""The rasteriser's host state (guassianhand_amd/_raster_state.py, round 5): one _DeviceState per device behind a re-entrant lock,
 process-wide switches in _Policy, the GH_FLAG_DEPTH24 verdict learned from read-backs only. No GPU: the state objects and the
 pure host logic."""
 import threading

@@ -2,7 +2,7 @@
 import os, sys, time, gc
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch, ctypes as C
-from guassianhand_amd import rasterizer as R
+from guassianhand_amd import _raster_launch as RL   # the module that resolves _ptr
 from guassianhand_amd.camera import Camera
 from guassianhand_amd.renderer import GaussianModel
 from tests.helpers import forward_single_view
@@ -24,7 +24,7 @@ def timed_ptr(t):
     k = (tuple(t.shape), str(t.dtype)[6:], t.requires_grad, type(t.grad_fn).__name__ if t.grad_fn is not None else "leaf")
     e = acc.setdefault(k, [0, 0.0, 0.0]); e[0] += 1; e[1] += t1 - t0; e[2] += t2 - t1
     return p
-R._ptr = timed_ptr
+RL._ptr = timed_ptr
 def step():
     gs.xyz.grad = None
     out = forward_single_view(gs, cam, sc.bg, **kw)

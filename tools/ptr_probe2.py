@@ -3,7 +3,7 @@ usage: python tools/ptr_probe2.py <variant>   variants: plain | nogc | sameptr |
 import os, sys, time, gc
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch, ctypes as C
-from guassianhand_amd import rasterizer as R
+from guassianhand_amd import _raster_launch as RL   # the module that resolves _ptr
 from guassianhand_amd.camera import Camera
 from guassianhand_amd.renderer import GaussianModel
 from tests.helpers import forward_single_view
@@ -17,7 +17,7 @@ kw = dict(color_w=sc.color_w, xyz_b=sc.xyz_b, color_b=sc.color_b, opacity_b=sc.o
 if variant == "sameptr":
     def _ptr(t):
         return None if t is None else C.c_void_p(t.data_ptr())
-    R._ptr = _ptr
+    RL._ptr = _ptr
 def step():
     gs.xyz.grad = None
     out = forward_single_view(gs, cam, sc.bg, **kw)

@@ -2,7 +2,7 @@
 import os, sys, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch, ctypes as C
-from guassianhand_amd import rasterizer as R, _abi
+from guassianhand_amd import _raster_launch as RL, _abi   # RL: the module that resolves _ptr / _inputs_struct
 from guassianhand_amd.camera import Camera
 from guassianhand_amd.renderer import GaussianModel
 from tests.helpers import forward_single_view
@@ -19,14 +19,14 @@ def inputs_struct(c, with_shs=True, bound=None):
     vals = []
     for k in names:
         t0 = time.perf_counter()
-        v = R._ptr(t[k]) if (k != "shs" or with_shs) else None
+        v = RL._ptr(t[k]) if (k != "shs" or with_shs) else None
         T[("ptr", k, with_shs)] = T.get(("ptr", k, with_shs), 0.0) + time.perf_counter() - t0
         vals.append(v)
     t0 = time.perf_counter()
-    r = _abi.GhInputs(*vals, R._ptr(bound), R._ptr(t["cov3D"]))
+    r = _abi.GhInputs(*vals, RL._ptr(bound), RL._ptr(t["cov3D"]))
     T[("struct", "", with_shs)] = T.get(("struct", "", with_shs), 0.0) + time.perf_counter() - t0
     return r
-R._inputs_struct = inputs_struct
+RL._inputs_struct = inputs_struct
 def step():
     gs.xyz.grad = None
     out = forward_single_view(gs, cam, sc.bg, **kw)
