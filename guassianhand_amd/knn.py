@@ -11,6 +11,18 @@ is not part of the reference tree):
 `knn_points(p, p, K)` mirrors the reference call for the self-query case and returns the same 3-tuple shape
 (dists (B,N,K), idx (B,N,K) int64, None); `interaction_mask` is the whole four-line block. ROCm tensors only: the
 kernels raise if the library is missing and there is no CPU path.
+
+Where "exact" holds. The index lists and squared distances are bit-equal to a brute-force float32 computation (ties by ascending
+index) whenever the squared distance between any two DISTINCT points is a normal float32 number, i.e. no two distinct points are
+closer than about 1e-19 (sqrt(FLT_MIN)); identical points are always exact, at any number of copies. Hands are in metres, so every
+real cloud is inside this domain by some fifteen orders of magnitude. Below it (a cloud so small that squared distances underflow
+to 0) the lists are still in range and unique per row, but they are not the brute-force lists, which order the tied zeros by
+index: the query kernel's stop rule compares the K-th squared distance with ((r - 0.001) * h)^2, which underflows
+with it, so `0 <= 0` ends the walk as soon as K candidates exist, before the cells holding the lowest indices are visited. The fix is
+two lines in gh_knn_query_kernel, recorded here for the next change that touches csrc/: never stop at r = 0 unless h = 0, and for
+r > 0 stop only when rg * rg >= FLT_MIN. Non-finite points are contained: the walk is bounded by the grid, a NaN or infinite point
+never enters the list of a finite point while K finite points exist, and its own row holds in-range indices.
+tests/test_gpu_knn_edges.py checks all of this (scalings by 2^+-40 inside the domain, 2^-100 below it).
 """
 from __future__ import annotations
 
