@@ -340,10 +340,30 @@ def declare_attn(lib: C.CDLL) -> None:
         [C.c_void_p, C.c_size_t, C.c_void_p]
 
 
-ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS
+# ---- include/gh_uvd.h: the UV search (a header of its own, as gh_attn.h is) ----
+GH_UVD_MAX_SPLIT = 16
+GH_UVD_REC_BYTES = 80
+GH_UVD_TARGET_WGS = 8192
+GH_UVD_MIN_CHUNK = 128
+
+UVD_SYMBOLS = ("gh_uvd_workspace_bytes", "gh_uvd_auto_split", "gh_uvd_forward")
+
+
+def declare_uvd(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_uvd.h declares."""
+    lib.gh_uvd_workspace_bytes.restype = C.c_size_t
+    lib.gh_uvd_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gh_uvd_auto_split.restype = C.c_int
+    lib.gh_uvd_auto_split.argtypes = [C.c_int, C.c_int]
+    lib.gh_uvd_forward.restype = C.c_int
+    lib.gh_uvd_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + \
+        [C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the seven headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn):
+    """Attach argtypes/restypes for every symbol of the eight headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd):
         one(lib)

@@ -24,6 +24,12 @@ attention core of `self_attn_layer`, which `forward` applies to the points `mink
 kernels (include/gh_attn.h) while its dropout is inactive (eval mode); in train mode it keeps the reference's torch statements.
 `GS3DRendererFusedAllFetchAttn` / `GS3DRendererEditFusedAllFetchAttn`: gate, refinement, head, fetch and attention. Opt-in too.
 
+`GS3DRendererFusedUvd` / `GS3DRendererEditFusedUvd`: `configure()` additionally calls `uvd.fuse_get_uvd(self)` — `forward_single_batch`'s
+`get_uvd` (every Gaussian's closest point on the UV-topology hand mesh, whose UV drives the `color_b` / `opacity_b` lookups) then runs
+the HIP UV search (include/gh_uvd.h) instead of livehand's. `GS3DRendererFusedAllFetchAttnUvd` / `GS3DRendererEditFusedAllFetchAttnUvd`:
+gate, refinement, head, fetch, attention and UV search. Opt-in too. The reference's modules import livehand at their top, which
+`uvd.install_livehand_shim()` serves where livehand is absent: resolving one of these four names calls it first.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
@@ -36,6 +42,7 @@ _SUFFIXES = {"FusedHead": (False, True, False, False, "the fused Gaussian head")
              "FusedAllFetch": (True, True, True, False, "the fused gate and refinement, Gaussian head and plane fetch"),
              "FusedAttn": (False, False, False, True, "the HIP attention core"),
              "FusedAllFetchAttn": (True, True, True, True, "the fused gate and refinement, Gaussian head, plane fetch and HIP attention core")}
+_UVD = {"FusedUvd": "", "FusedAllFetchAttnUvd": "FusedAllFetchAttn"}          # suffix -> the suffix of the class the UV search is added to
 
 
 def _build(name):
@@ -64,6 +71,17 @@ def _build(name):
                     fuse_self_attn(self)
 
             return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
+    for suffix, inner in _UVD.items():
+        if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
+            from .uvd import fuse_get_uvd, install_livehand_shim
+            install_livehand_shim()                            # the base's module imports livehand.input_encoder at its top
+            base = __getattr__(name[:-len(suffix)] + inner)
+
+            def configure(self, *args, **kwargs):
+                base.configure(self, *args, **kwargs)
+                fuse_get_uvd(self)
+
+            return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and the HIP UV search"})
     raise AttributeError(name)
 
 

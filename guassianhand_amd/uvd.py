@@ -1,0 +1,284 @@
+"""The UV search: for every point its closest point on a triangle mesh that carries per-corner UVs, and that point's UV and distance —
+what the reference asks of `livehand.input_encoder.get_uvd` (infer_one_shot.py:229 on the input points, renderer_one_shot.py:481 on
+the pruned and duplicated points, whose UVs drive the `color_b` / `opacity_b` lookups) — on the device through include/gh_uvd.h.
+
+    closest_uv(points, verts, faces, face_uv, *, split=0, ops="fused") -> (uv (N,2), d (N,), face (N,) int64, bary (N,3))
+    get_uvd(points, verts, faces, face_uv_xy, **kw) -> (uv, d, {"face": ..., "bary": ...})       the reference's argument order
+    closest_uv_ref(points, verts, faces, face_uv, *, acc=None)                                  the plain-torch restatement
+
+The contract is the one at the top of include/gh_uvd.h: the winner is the lexicographic minimum of (squared distance as computed,
+face index) over the valid faces; barycentrics are >= 0 exactly, so a UV never leaves the hull of its face's corner UVs; the distance
+is unsigned; a point without a winner (non-finite coordinate, no valid face) gets face = -1 and NaNs. The block is specified by that
+mathematics and is NOT pinned against livehand's implementation, whose source this project has never had: the reference's callers
+fix the argument order, the (N,2) first element that is written in place after `unsqueeze(0)`, and u / 1, v / 0.5 in [0, 1]; the
+second element is read by nothing after a concatenation and the third by nothing at all. The third element here carries the face and
+the barycentrics, so a caller who needs a signed distance can sign it.
+
+ROCm float32 tensors go through the HIP kernels only. `closest_uv_ref` (chunked over points, float64 on request) runs for CPU
+tensors, for `ops="torch"` and for other dtypes; it is the tests' yardstick.
+
+Gradients. When `points`, `verts` or `face_uv` requires a gradient and grad mode is on, the winning face is taken from the kernel (or
+from the restatement) as a constant, and that one face's closest point, barycentrics, UV and distance are recomputed per point in
+plain torch on the gathered rows: O(N) elementwise work that autograd differentiates, the region clamps passing gradients the way
+`torch.clamp` does. There is no hand-written backward kernel, and no shipped path needs one: in the one-shot fit the points are data
+(infer_one_shot.py:340-343 trains maps, not points), and in pretraining `color_b` is None, so the UVs are consumed by nothing.
+
+`fuse_get_uvd(renderer)` sets `renderer.get_uvd`, the hook `renderer.forward_single_batch` / `forward_single_batch_edit` read;
+`install_livehand_shim()` serves the reference's module-level `from livehand.input_encoder import ...` when livehand is absent."""
+from __future__ import annotations
+
+import importlib.util
+import sys
+import types
+from typing import Optional, Tuple
+
+import torch
+
+from . import _abi
+from ._call import launch, lib, ptr, workspace
+
+MAX_SPLIT = _abi.GH_UVD_MAX_SPLIT
+_REF_PAIRS = 1 << 22                     # point-face pairs per chunk of the restatement: (n, F) temporaries of 16 MB in float32
+
+
+def auto_split(N: int, F: int) -> int:
+    """The split that split=0 stands for (gh_uvd_auto_split: pure host arithmetic, stated in include/gh_uvd.h)."""
+    return int(lib().gh_uvd_auto_split(int(N), int(F)))
+
+
+# ---- plain-torch restatement (CPU path, the differentiable path and the yardstick of the device path) --------------------------------
+def _degenerate_share(dtype: torch.dtype) -> float:
+    return 2.0 ** -15 if dtype == torch.float32 else 2.0 ** -35      # about eps ** (2 / 3): include/gh_uvd.h, "Zero area"
+
+
+def _recip(d: torch.Tensor) -> torch.Tensor:
+    pos = (d > 0).detach()
+    r = 1.0 / torch.where(pos, d, torch.ones_like(d))
+    return torch.where(pos & torch.isfinite(r), r, torch.zeros_like(d))
+
+
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def _records(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
+    """The face records of gh_uvd.hip from corner positions (..., 3), as tuples of components."""
+    A = a.unbind(-1)
+    ab, ac, bc = (b - a).unbind(-1), (c - a).unbind(-1), (c - b).unbind(-1)
+    d00, d01, d11 = _dot(ab, ab), _dot(ab, ac), _dot(ac, ac)
+    den = d00 * d11 - d01 * d01
+    area = (den > _degenerate_share(a.dtype) * (d00 * d11)).detach()
+    iden = torch.where(area, _recip(den), torch.zeros_like(den))
+    return A, ab, ac, bc, d00, d01, d11, _recip(d00), _recip(d11), _recip(_dot(bc, bc)), iden
+
+
+def _clamp01(t: torch.Tensor) -> torch.Tensor:
+    return torch.clamp(torch.where(torch.isnan(t), torch.zeros_like(t), t), 0.0, 1.0)
+
+
+def _closest(p, rec, full: bool):
+    """ghu_closest statement for statement (sums of products in place of its fmaf chains): p a tuple of three components that
+    broadcast against the record's. -> s, and (b0, b1, b2) when `full`."""
+    A, ab, ac, bc, d00, d01, d11, i00, i11, ibc, iden = rec
+    ap = tuple(p[k] - A[k] for k in range(3))
+    d1, d2 = _dot(ab, ap), _dot(ac, ap)
+    v = (d11 * d1 - d01 * d2) * iden
+    w = (d00 * d2 - d01 * d1) * iden
+    u = (1.0 - v) - w
+    inside = ((iden > 0) & (v >= 0) & (w >= 0) & (u >= 0)).detach()
+    ri = tuple(ap[k] - v * ab[k] - w * ac[k] for k in range(3))
+    s = torch.where(inside, _dot(ri, ri), torch.full_like(v, float("inf")))
+    t1 = _clamp01(d1 * i00)
+    r1 = tuple(ap[k] - t1 * ab[k] for k in range(3))
+    s_ab = _dot(r1, r1)
+    t2 = _clamp01(d2 * i11)
+    r2 = tuple(ap[k] - t2 * ac[k] for k in range(3))
+    s_ac = _dot(r2, r2)
+    bp = tuple(ap[k] - ab[k] for k in range(3))
+    t3 = _clamp01(_dot(bc, bp) * ibc)
+    r3 = tuple(bp[k] - t3 * bc[k] for k in range(3))
+    s_bc = _dot(r3, r3)
+    if not full:
+        s = torch.where(s_ab < s, s_ab, s)
+        s = torch.where(s_ac < s, s_ac, s)
+        return torch.where(s_bc < s, s_bc, s), None
+    zero = torch.zeros_like(v)
+    b = (torch.clamp(u, min=0.0), v, w)
+    for cand, bc_ in ((s_ab, (1.0 - t1, t1, zero)), (s_ac, (1.0 - t2, zero, t2)), (s_bc, (zero, 1.0 - t3, t3))):
+        lt = (cand < s).detach()
+        s = torch.where(lt, cand, s)
+        b = tuple(torch.where(lt, n, o) for n, o in zip(bc_, b))
+    return s, b
+
+
+def _safe_faces(verts: torch.Tensor, faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(faces with every index inside [0, V), valid (F,) bool): indices in range and nine finite coordinates."""
+    V = verts.shape[0]
+    inside = ((faces >= 0) & (faces < V)).all(1)
+    safe = faces.clamp(0, V - 1)
+    return safe, inside & torch.isfinite(verts.detach()[safe]).all(2).all(1)
+
+
+def _outputs(points, verts, faces, face_uv, face):
+    """The winner's closest point per point, in plain torch on the gathered rows: (uv, d, bary). Differentiable with respect to
+    points, verts and face_uv; `face` (N,) int64 is a constant, -1 giving NaNs."""
+    won = face >= 0
+    rows = faces[face.clamp(min=0)].clamp(0, verts.shape[0] - 1)
+    a, b, c = verts[rows[:, 0]], verts[rows[:, 1]], verts[rows[:, 2]]
+    s, bary = _closest(points.unbind(-1), _records(a, b, c), True)
+    t = face_uv[face.clamp(min=0)]
+    uv = bary[0][:, None] * t[:, 0] + bary[1][:, None] * t[:, 1] + bary[2][:, None] * t[:, 2]
+    pos = (s > 0).detach()
+    d = torch.where(pos, torch.sqrt(torch.where(pos, s, torch.ones_like(s))), torch.zeros_like(s))   # no 0 * inf in sqrt's backward
+    d = torch.where(torch.isnan(s), s, d)
+    nan = torch.full_like(s, float("nan"))
+    bary = torch.stack([torch.where(won, x, nan) for x in bary], 1)
+    return torch.where(won[:, None], uv, nan[:, None]), torch.where(won, d, nan), bary
+
+
+def _search_ref(points, verts, faces, valid) -> torch.Tensor:
+    """The winning face per point, (N,) int64, -1 without a winner: all pairs, chunked over points."""
+    N, F = points.shape[0], faces.shape[0]
+    rec = _records(verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]])
+    rec = tuple(tuple(x[None] for x in r) if isinstance(r, tuple) else r[None] for r in rec)
+    ids = torch.arange(F, device=points.device)[None]
+    out = torch.empty(N, dtype=torch.int64, device=points.device)
+    step = max(1, _REF_PAIRS // max(F, 1))
+    inf = float("inf")
+    for i in range(0, N, step):
+        p = points[i:i + step]
+        s, _ = _closest(tuple(p[:, k:k + 1] for k in range(3)), rec, False)
+        s = torch.where(valid[None] & ~torch.isnan(s), s, torch.full_like(s, inf))
+        smin = s.min(1).values
+        first = torch.where(s == smin[:, None], ids, torch.full_like(ids, F)).min(1).values          # equal s: the lowest face index
+        out[i:i + step] = torch.where(smin < inf, first, torch.full_like(first, -1))
+    return out
+
+
+def _check(points, verts, faces, face_uv) -> None:
+    for name, t, shape in (("points", points, "(N, 3)"), ("verts", verts, "(V, 3)"), ("faces", faces, "(F, 3)")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if face_uv.dim() != 3 or tuple(face_uv.shape) != (faces.shape[0], 3, 2):
+        raise ValueError(f"face_uv: expected ({faces.shape[0]}, 3, 2), got {tuple(face_uv.shape)}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"faces: expected int32 or int64, got {faces.dtype}")
+    if faces.shape[0] < 1 or verts.shape[0] < 1:
+        raise ValueError(f"the mesh needs at least one vertex and one face, got V={verts.shape[0]}, F={faces.shape[0]}")
+    for name, t in (("verts", verts), ("faces", faces), ("face_uv", face_uv)):
+        if t.device != points.device:
+            raise ValueError(f"{name} is on {t.device}, points on {points.device}")
+
+
+def closest_uv_ref(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, face_uv: torch.Tensor, *,
+                   acc: Optional[torch.dtype] = None):
+    """The contract of include/gh_uvd.h in plain torch on the tensors' device -> (uv, d, face int64, bary). Chunked over points, so
+    that N = 98,562 on F = 3,076 faces stays within a few hundred MB. acc=torch.float64 computes (and returns) in double."""
+    _check(points, verts, faces, face_uv)
+    dtype = acc if acc is not None else points.dtype
+    with torch.no_grad():
+        points, verts, face_uv = points.to(dtype), verts.to(dtype), face_uv.to(dtype)
+        faces, valid = _safe_faces(verts, faces.long())
+        face = _search_ref(points, verts, faces, valid)
+        uv, d, bary = _outputs(points, verts, faces, face_uv, face)
+        return uv, d, face, bary
+
+
+# ---- device path ---------------------------------------------------------------------------------------------------------------
+def _search_device(points, verts, faces, face_uv, split: int):
+    """One gh_uvd_forward on the current stream -> (uv, d, face int32, bary), fresh tensors."""
+    N, V, F, dev = points.shape[0], verts.shape[0], faces.shape[0], points.device
+    points, verts, face_uv = points.detach().contiguous(), verts.detach().contiguous(), face_uv.detach().contiguous()
+    if faces.dtype != torch.int32:                       # an index beyond int32 is beyond V as well
+        faces = torch.where((faces >= 0) & (faces < V), faces, torch.full_like(faces, -1)).to(torch.int32)
+    faces = faces.contiguous()
+    uv = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    d = torch.empty(N, dtype=torch.float32, device=dev)
+    face = torch.empty(N, dtype=torch.int32, device=dev)
+    bary = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    if N > 0:
+        nbytes = int(lib().gh_uvd_workspace_bytes(N, F, split))
+        ws = workspace(nbytes, dev)
+        launch("gh_uvd_forward", dev, ptr(points), N, ptr(verts), V, ptr(faces), ptr(face_uv), F, split, ptr(uv), ptr(d), ptr(face),
+               ptr(bary), ptr(ws), nbytes, what=f"gh_uvd_forward (N={N}, V={V}, F={F}, split={split})")
+    return uv, d, face, bary
+
+
+def closest_uv(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, face_uv: torch.Tensor, *, split: int = 0,
+               ops: str = "fused"):
+    """points (N,3), verts (V,3), faces (F,3) int32 or int64, face_uv (F,3,2) -> (uv (N,2), d (N,), face (N,) int64, bary (N,3)): the
+    contract of include/gh_uvd.h. split: the number of face chunks searched side by side, 0 for the library's choice; the outputs do
+    not depend on it. ops="torch" runs the plain-torch restatement on the tensors' device. Differentiable with respect to points,
+    verts and face_uv through the winning face (module docstring)."""
+    if ops not in ("fused", "torch"):
+        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    if not 0 <= int(split) <= MAX_SPLIT:
+        raise ValueError(f"split must lie in [0, {MAX_SPLIT}], got {split}")
+    _check(points, verts, faces, face_uv)
+    need_grad = torch.is_grad_enabled() and (points.requires_grad or verts.requires_grad or face_uv.requires_grad)
+    fused = ops == "fused" and points.is_cuda and all(t.dtype == torch.float32 for t in (points, verts, face_uv))
+    if not fused:
+        out = closest_uv_ref(points, verts, faces, face_uv)
+        if not need_grad:
+            return out
+        face = out[2]
+    else:
+        out = _search_device(points, verts, faces, face_uv, int(split))
+        face = out[2].long()
+        if not need_grad:
+            return out[0], out[1], face, out[3]
+    dtype = points.dtype
+    uv, d, bary = _outputs(points, verts.to(dtype), _safe_faces(verts, faces.long())[0], face_uv.to(dtype), face)
+    return uv, d, face, bary
+
+
+def get_uvd(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, face_uv_xy: torch.Tensor, **kw):
+    """livehand.input_encoder.get_uvd's call as the reference makes it — get_uvd(points (N,3), vert3d_uv[0] (V,3), face_uv (F,3) long,
+    face_uv_xy (F,3,2)), unbatched — over closest_uv: (uv (N,2), d (N,), {"face": (N,) int64, "bary": (N,3)}). `uv` is a fresh,
+    contiguous tensor every call: the caller writes into it in place. Keywords are closest_uv's."""
+    uv, d, face, bary = closest_uv(points, verts, faces, face_uv_xy, **kw)
+    return uv.contiguous(), d, {"face": face, "bary": bary}
+
+
+def fuse_get_uvd(renderer, **kw):
+    """Set `renderer.get_uvd`, the hook renderer.forward_single_batch and forward_single_batch_edit read before they reach for
+    livehand. Keywords (split=, ops=) are bound into the hook. Nothing else of the object changes. Returns the renderer."""
+    hook = get_uvd if not kw else (lambda points, verts, faces, face_uv_xy: get_uvd(points, verts, faces, face_uv_xy, **kw))
+    object.__setattr__(renderer, "get_uvd", hook)
+    return renderer
+
+
+# ---- the reference's module-level import ---------------------------------------------------------------------------------------------
+def _never_called(name: str):
+    def stub(*args, **kwargs):
+        raise NotImplementedError(f"livehand.input_encoder.{name} is not provided by guassianhand_amd: the reference imports the name "
+                                  "and never calls it")
+    stub.__name__ = name
+    return stub
+
+
+def install_livehand_shim(force: bool = False) -> bool:
+    """Register `livehand` and `livehand.input_encoder` in sys.modules with this module's get_uvd, for the reference's
+    `from livehand.input_encoder import read_mano_uv_obj, save_obj_for_debugging, get_uvd` (infer_one_shot.py:33,
+    renderer_one_shot.py:19 and both _edit files). The other two names raise NotImplementedError when called. Registers only when
+    the real package cannot be imported, or when `force` is set. -> whether the shim is in place."""
+    have = sys.modules.get("livehand")
+    if have is not None and getattr(have, "__gh_uvd_shim__", False):
+        return True
+    if not force:
+        try:
+            real = have is not None or importlib.util.find_spec("livehand") is not None
+        except (ImportError, ValueError):
+            real = False
+        if real:
+            return False
+    pkg, enc = types.ModuleType("livehand"), types.ModuleType("livehand.input_encoder")
+    pkg.__doc__ = enc.__doc__ = "Stand-in registered by guassianhand_amd.uvd.install_livehand_shim: get_uvd over the HIP UV search."
+    pkg.__path__ = []
+    pkg.__gh_uvd_shim__ = enc.__gh_uvd_shim__ = True
+    enc.get_uvd = get_uvd
+    enc.read_mano_uv_obj = _never_called("read_mano_uv_obj")
+    enc.save_obj_for_debugging = _never_called("save_obj_for_debugging")
+    pkg.input_encoder = enc
+    sys.modules["livehand"], sys.modules["livehand.input_encoder"] = pkg, enc
+    return True
