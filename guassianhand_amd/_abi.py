@@ -360,10 +360,49 @@ def declare_uvd(lib: C.CDLL) -> None:
         [C.c_void_p, C.c_size_t, C.c_void_p]
 
 
-ALL_SYMBOLS = EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS
+# ---- include/gh_cond.h: the point conditioning (a header of its own, as gh_uvd.h is) ----
+GH_COND_ROWS = 64
+GH_COND_MAX_LEVELS = 8
+GH_COND_MAX_CODE = 64
+GH_COND_MAX_HD = 64
+
+COND_SYMBOLS = ("gh_cond_width", "gh_cond_fold_bytes", "gh_cond_rows", "gh_cond_fold", "gh_cond_mlp_forward", "gh_cond_mlp_backward")
+COND_PARAMS = ("ln_weight", "ln_bias", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")
+
+
+class GhCondRows(C.Structure):
+    """The segments of the varying row: uv (P,2), xyz (P,3), flag (P,), code (P,Cc) through code_stride; absent ones are NULL."""
+    _fields_ = [("uv", C.c_void_p), ("xyz", C.c_void_p), ("flag", C.c_void_p), ("code", C.c_void_p), ("code_stride", C.c_int64),
+                ("Cc", C.c_int32), ("levels", C.c_int32)]
+
+
+class GhCondParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in COND_PARAMS]
+
+
+def declare_cond(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_cond.h declares."""
+    R, Pm = C.POINTER(GhCondRows), C.POINTER(GhCondParams)
+    lib.gh_cond_width.restype = C.c_int
+    lib.gh_cond_width.argtypes = [R]
+    lib.gh_cond_fold_bytes.restype = C.c_size_t
+    lib.gh_cond_fold_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gh_cond_rows.restype = C.c_int
+    lib.gh_cond_rows.argtypes = [R, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gh_cond_fold.restype = C.c_int
+    lib.gh_cond_fold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, Pm, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gh_cond_mlp_forward.restype = C.c_int
+    lib.gh_cond_mlp_forward.argtypes = [R, C.c_int, C.c_int, C.c_int, C.c_int, Pm, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    lib.gh_cond_mlp_backward.restype = C.c_int
+    lib.gh_cond_mlp_backward.argtypes = [R, C.c_int, C.c_int, C.c_int, C.c_int, Pm, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p]
+
+
+ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
+               COND_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the eight headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd):
+    """Attach argtypes/restypes for every symbol of the nine headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond):
         one(lib)

@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from . import _abi
 from ._call import launch, lib, ptr, row_stride, rows, workspace
+from .cond import PointRows
 
 _REDUCE = {"max": _abi.GH_POOL_MAX, "mean": _abi.GH_POOL_MEAN}
 
@@ -357,23 +358,32 @@ def cell_index(p: torch.Tensor, radius: float, plane_size: int) -> torch.Tensor:
     return xi[..., 0] + plane_size * xi[..., 1]
 
 
-def pointnet_forward(self, p: torch.Tensor, ops: Optional[str] = None) -> torch.Tensor:
+def pointnet_forward(self, p, ops: Optional[str] = None) -> torch.Tensor:
     """LocalPoolPointnet.forward(p) (pointnet_texture.py:89-114) over one PoolPlan per cloud: (B,T,D) -> (B, c_dim, plane, plane).
     Reads self.cfg.{radius, plane_size, scatter_type}, self.fc_pos, self.blocks, self.fc_c. ops="torch" runs the plain-torch
-    restatement of the pooling on p's device instead of the kernels. A list in self.pool_record receives every pooled tensor."""
+    restatement of the pooling on p's device instead of the kernels. A list in self.pool_record receives every pooled tensor.
+    `p` may be a cond.PointRows standing for the (B,T,D) concatenation: the cell index then comes from its uv columns and the first
+    layer from PointRows.linear(self.fc_pos); the concatenation is not built."""
     ops = ops or getattr(self, "pool_ops", "fused")
     if ops not in ("fused", "torch"):
         raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
-    if p.dim() != 3:
+    given = isinstance(p, PointRows)
+    if not given and p.dim() != 3:
         raise ValueError(f"p: expected (B, T, D), got {tuple(p.shape)}")
     cfg = self.cfg
     reduce, ps = str(cfg.scatter_type), int(cfg.plane_size)
     _check_reduce(reduce)
     record = getattr(self, "pool_record", None)
-    index = cell_index(p, float(cfg.radius), ps)
-    net = self.blocks[0](self.fc_pos(p))
+    if given:
+        n_clouds = p.B
+        index = cell_index(p.uv_columns(), float(cfg.radius), ps)
+        net = self.blocks[0](p.linear(self.fc_pos, ops))
+    else:
+        n_clouds = p.shape[0]
+        index = cell_index(p, float(cfg.radius), ps)
+        net = self.blocks[0](self.fc_pos(p))
     planes = []
-    for b in range(p.shape[0]):
+    for b in range(n_clouds):
         plan = PoolPlan(index[b], ps * ps)
         nb = net[b]
         for block in self.blocks[1:]:
@@ -387,7 +397,7 @@ def pointnet_forward(self, p: torch.Tensor, ops: Optional[str] = None) -> torch.
         c = self.fc_c(nb)
         planes.append(plane_mean(c, plan) if ops == "fused" else _plane_mean_ref(c, plan))
     fea = torch.stack(planes)
-    return fea.reshape(p.shape[0], fea.shape[1], ps, ps)
+    return fea.reshape(n_clouds, fea.shape[1], ps, ps)
 
 
 class LocalPoolPointnet(nn.Module):
