@@ -1,5 +1,5 @@
 """What the Python wrappers of the C-ABI share: the loaded library, the ctypes forms of tensors and streams, the rows-in-place rule,
-the host-side argument check and the one way an entry point is called. _raster_launch.py keeps wrappers of its own (its pointers are plain
+the host-side argument checks, the null-cotangent rule and the one way an entry point is called. _raster_launch.py keeps wrappers of its own (its pointers are plain
 integers for struct fields, and its stream and device handling were tuned for the render loop)."""
 from __future__ import annotations
 
@@ -53,7 +53,18 @@ def check_f32(x: torch.Tensor, named) -> None:
             raise ValueError(f"{name} is on {t.device}, x on {x.device}")
 
 
-def launch(name: str, dev, *args, what: Optional[str] = None, detail: str = "") -> None:
+def check_ops(ops: str) -> None:
+    if ops not in ("fused", "torch"):
+        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+
+
+def cotangent(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """An incoming gradient as the kernels read it: float32, contiguous; None (no gradient arrived) stays None, the entry points'
+    null cotangent."""
+    return None if g is None else g.float().contiguous()
+
+
+def launch(name: str, dev,*args, what: Optional[str] = None, detail: str = "") -> None:
     """Call the entry point `name` with dev's current stream appended, dev being the current device; raise on a non-zero status."""
     with torch.cuda.device(dev):
         rc = getattr(lib(), name)(*args, stream(dev))

@@ -36,7 +36,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import launch, lib, ptr, workspace
+from ._call import check_ops, launch, lib, ptr, workspace
 
 HEAD_DIM = _abi.GH_ATTN_D
 
@@ -134,8 +134,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, norm=None, o
     than float32 (float64, or the half types a module yields under autocast) always take it.
     return_lse=True also returns ln sum exp(score) per row, (BS, H, V), not differentiable: what the kernels keep for the backward,
     exposed so that the tests can check its bits under a permutation of the rows."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     _check(q, k, v)
     norm = _norm_of(q, norm)
     if not norm > 0:

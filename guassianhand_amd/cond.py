@@ -34,7 +34,8 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import launch, lib, ptr, row_stride, rows as _rows_in_place, struct
+from ._call import check_ops, cotangent, launch, lib, ptr, row_stride, rows as _rows_in_place, struct
+from ._mlp_block import _MLPBlock, block_params as _block_params, dropout_live, init_linears
 
 PARAMS = _abi.COND_PARAMS                                        # the order of cond_mlp's `params` (GhCondParams)
 MAX_LEVELS, MAX_CODE, MAX_HD = _abi.GH_COND_MAX_LEVELS, _abi.GH_COND_MAX_CODE, _abi.GH_COND_MAX_HD
@@ -129,7 +130,7 @@ class _CondMlpFn(torch.autograd.Function):
         if codes is not None and ctx.needs_input_grad[0]:
             dcode = torch.empty(P, codes.shape[1], dtype=torch.float32, device=codes.device)
             if P > 0:
-                g = None if g_out is None else g_out.float().contiguous()
+                g = cotangent(g_out)
                 ps = struct(_abi.GhCondParams, [w2] * 6)              # (the backward reads fc2_weight; the rest reach it through fold)
                 d = _desc(uv, xyz, flag, codes, levels)
                 launch("gh_cond_mlp_backward", codes.device, C.byref(d), P, N, De, Hd, C.byref(ps), ptr(fold), float(eps), ptr(g),
@@ -254,8 +255,7 @@ def _mlp_kernel_ok(rows: PointRows, params) -> bool:
 def cond_mlp(rows: PointRows, params: Sequence[torch.Tensor], eps: float = 1e-6, ops: str = "fused") -> torch.Tensor:
     """rows -> (B,N,Hd): fc2(relu(fc1(LayerNorm(rows.dense())))) with params in PARAMS order: LayerNorm weight and bias (D = Dv + De),
     fc1 (Hd,D) and its bias, fc2 (Hd,Hd) and its bias. ops="torch" runs the plain-torch restatement on the rows' device."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     params = tuple(params)
     if len(params) != len(PARAMS):
         raise ValueError(f"params: expected the {len(PARAMS)} tensors {PARAMS}, got {len(params)}")
@@ -273,36 +273,12 @@ def cond_mlp(rows: PointRows, params: Sequence[torch.Tensor], eps: float = 1e-6,
 
 
 # ---- the module and the seam ---------------------------------------------------------------------------------------------------------
-class _MLPBlock(nn.Module):
-    """The reference's MLP_block (verts_refinement.py:16-32): the sub-module names are its state-dict keys."""
-
-    def __init__(self, in_dim: int, hid_dim: int, dropout: float = 0.1):
-        super().__init__()
-        self.layer_norm = nn.LayerNorm(in_dim, eps=1e-6)
-        self.fc1 = nn.Linear(in_dim, hid_dim)
-        self.fc2 = nn.Linear(hid_dim, hid_dim)
-        self.dropout1 = nn.Dropout(dropout)
-        self.dropout2 = nn.Dropout(dropout)
-
-    def forward(self, x):
-        return self.dropout2(self.fc2(self.dropout1(F.relu(self.fc1(self.layer_norm(x))))))
-
-
-def _block_params(ff):
-    return [ff.layer_norm.weight, ff.layer_norm.bias, ff.fc1.weight, ff.fc1.bias, ff.fc2.weight, ff.fc2.bias]
-
-
-def _dropout_active(module) -> bool:
-    ff = module.ff1
-    return bool(module.training) and any(float(getattr(d, "p", 0.0)) > 0 for d in (ff.dropout1, ff.dropout2))
-
-
 def module_forward(module, rows: PointRows, ops: str = "fused") -> torch.Tensor:
     """additional_features_fc.forward over a PointRows. With dropout live (train mode, p > 0) the module's own forward runs over
     rows.dense(), exactly the reference's statements; otherwise cond_mlp over the module's own parameters."""
-    if _dropout_active(module):
-        return module(rows.dense())
     ff = module.ff1
+    if dropout_live(module, ff):
+        return module(rows.dense())
     return cond_mlp(rows, _block_params(ff), eps=float(ff.layer_norm.eps), ops=ops)
 
 
@@ -315,10 +291,7 @@ class AdditionalFeaturesFC(nn.Module):
         super().__init__()
         self.ff1 = _MLPBlock(int(f_dim_in), int(f_dim_out))
         self.cond_ops = ops
-        for m in self.modules():
-            if isinstance(m, nn.Linear):
-                nn.init.xavier_uniform_(m.weight)
-                nn.init.constant_(m.bias, 0.0)
+        init_linears(self)
 
     def forward(self, verts_f):
         if isinstance(verts_f, PointRows):

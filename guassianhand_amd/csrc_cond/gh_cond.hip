@@ -8,6 +8,7 @@
 //             over W1g with the per-batch terms in the epilogue, fc2. Wave w owns the outputs w, w + 4, ..., three at a time.
 //   backward  the same forward up to h1, W2^T . g gated in place, W1g^T . d1 with the two sums of the LayerNorm's backward gathered
 //             on the way, dcode for the code columns. One launch.
+// The moments and the two layer routines (ghr_moments, ghr_linear, ghr_linear_t) are csrc_rows/gh_rows.h's, shared with gh_vert.hip.
 // Weights are wave-uniform (scalar cache); the per-batch constants are per-lane loads: a tile may hold rows of several batch
 // elements. No atomics; every float sum has a fixed order that depends on the layout alone.
 #include "../../include/gh_cond.h"
@@ -17,7 +18,7 @@
 #define GHC_ROWS GH_COND_ROWS
 #define GHC_PI_F 3.14159274101257324219f  // float32(pi): f_l = float32(pi * 2^l) = float32(pi) * 2^l, the scaling being exact
 
-static_assert(GHC_ROWS == 64 && GHC_BLOCK == 4 * GHC_ROWS, "lane = row, four waves share a row's columns");
+static_assert(GHC_ROWS == GHR_ROWS, "the shared row routines' tile: lane = row, four waves share a row's columns");
 
 struct GhcIn {
   const float *uv, *xyz, *flag, *code;
@@ -71,14 +72,13 @@ __device__ __forceinline__ void ghc_build(float* s, int pitch, const GhcIn& in, 
 // ---- the rows alone --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GHC_BLOCK) void ghc_rows_kernel(GhcIn in, int P, float* __restrict__ out, long long out_stride) {
   extern __shared__ __attribute__((aligned(16))) float ghc_smem[];
-  const int tid = threadIdx.x, Dv = in.Dv, VP = Dv | 1;
-  const long long row0 = (long long)blockIdx.x * GHC_ROWS;
-  const int nrows = (int)((long long)P - row0 < GHC_ROWS ? (long long)P - row0 : GHC_ROWS);
-  ghc_build(ghc_smem, VP, in, row0, nrows, tid);
+  const GhrTile t = ghr_tile<GHC_ROWS>(P);
+  const int Dv = in.Dv, VP = Dv | 1;
+  ghc_build(ghc_smem, VP, in, t.row0, t.nrows, t.tid);
   __syncthreads();
-  for (int i = tid; i < nrows * Dv; i += GHC_BLOCK) {
+  for (int i = t.tid; i < t.nrows * Dv; i += GHC_BLOCK) {
     const int r = i / Dv, c = i - r * Dv;
-    out[(row0 + r) * out_stride + c] = ghc_smem[r * VP + c];
+    out[(t.row0 + r) * out_stride + c] = ghc_smem[r * VP + c];
   }
 }
 
@@ -148,70 +148,7 @@ __global__ __launch_bounds__(GHC_BLOCK) void ghc_fold_kernel(const float* __rest
   }
 }
 
-// ---- the row kernels' shared routines ---------------------------------------------------------------------------------------------
-// emit(j, sum_k in[k] * W[j, k]) for the lane's row: four partial sums (k mod 4), one fmaf per term, (s0 + s1) + (s2 + s3).
-// Wave w owns j = w, w + 4, ..., three at a time: one LDS read of the input against three fmaf with a wave-uniform weight.
-template <class F>
-__device__ __forceinline__ void ghc_linear(const float* xr, int n, const float* __restrict__ W, int m, int wave, F emit) {
-  const int n4 = n & ~3, tail = n & 3;
-  for (int j0 = wave; j0 < m; j0 += 12) {
-    const float* w[3];
-    float acc[3][4];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int j = j0 + 4 * u;
-      w[u] = W + (size_t)(j < m ? j : m - 1) * n;  // (outputs past m are computed and dropped)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) acc[u][s] = 0.f;
-    }
-#pragma unroll 2
-    for (int k = 0; k < n4; k += 4) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const float xv = xr[k + s];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][k + s], acc[u][s]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {  // column n4 + s belongs to partial sum s
-      if (s < tail) {
-        const float xv = xr[n4 + s];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][n4 + s], acc[u][s]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int j = j0 + 4 * u;
-      if (j < m) emit(j, (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]));
-    }
-  }
-}
-
-// emit(k, sum_i g[i] * W[i, k]) for the lane's row, one chain of fmaf in ascending i; wave w owns k = 16t + 4w .. 16t + 4w + 3
-template <class F>
-__device__ __forceinline__ void ghc_linear_t(const float* gr, int m, const float* __restrict__ W, int ncols, int wave, F emit) {
-  for (int k0 = 4 * wave; k0 < ncols; k0 += 16) {
-    const int c1 = k0 + 1 < ncols ? 1 : 0, c2 = k0 + 2 < ncols ? 2 : c1, c3 = k0 + 3 < ncols ? 3 : c2;  // (past the end: repeated, dropped)
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 2
-    for (int i = 0; i < m; ++i) {
-      const float g = gr[i];
-      const float* wr = W + (size_t)i * ncols + k0;
-      a0 = fmaf(g, wr[0], a0); a1 = fmaf(g, wr[c1], a1); a2 = fmaf(g, wr[c2], a2); a3 = fmaf(g, wr[c3], a3);
-    }
-    emit(k0, a0);
-    if (k0 + 1 < ncols) emit(k0 + 1, a1);
-    if (k0 + 2 < ncols) emit(k0 + 2, a2);
-    if (k0 + 3 < ncols) emit(k0 + 3, a3);
-  }
-}
-
-__device__ __forceinline__ float ghc_sum4(const float* s_red, int lane) {
-  return (s_red[lane] + s_red[GHC_ROWS + lane]) + (s_red[2 * GHC_ROWS + lane] + s_red[3 * GHC_ROWS + lane]);
-}
-
+// ---- the LayerNorm + MLP over the rows ------------------------------------------------------------------------------------------
 struct GhcRow {
   float rstd, dm;   // dm = m_e - mu
   const float* fb;  // the lane's batch element: m_e, M_e, c1[Hd], c2[Hd]
@@ -219,26 +156,14 @@ struct GhcRow {
 
 // build the rows, the LayerNorm's statistics, the rows centred in place (s_v holds v - mu), h1 = relu(pre1) in s_h
 __device__ __forceinline__ GhcRow ghc_forward_tile(float* s_red, float* s_v, float* s_h, int VP, int HP, const GhcIn& in, int P, int N,
-                                                   int De, int Hd, const float* __restrict__ fold, float eps, long long row0, int nrows,
-                                                   int tid, int lane, int wave) {
-  const int Dv = in.Dv, D = Dv + De;
-  ghc_build(s_v, VP, in, row0, nrows, tid);
+                                                   int De, int Hd, const float* __restrict__ fold, float eps, const GhrTile& t) {
+  const int Dv = in.Dv, D = Dv + De, lane = t.lane, wave = t.wave;
+  ghc_build(s_v, VP, in, t.row0, t.nrows, t.tid);
   __syncthreads();
   float* vr = s_v + lane * VP;
-  float s = 0.f;
-  for (int k = wave; k < Dv; k += 4) s += vr[k];
-  s_red[wave * GHC_ROWS + lane] = s;
-  __syncthreads();
-  const float m_v = ghc_sum4(s_red, lane) / (float)Dv;
-  float q = 0.f;
-  for (int k = wave; k < Dv; k += 4) {
-    const float d = vr[k] - m_v;
-    q = fmaf(d, d, q);
-  }
-  s_red[GHC_BLOCK + wave * GHC_ROWS + lane] = q;
-  __syncthreads();
-  const float M_v = ghc_sum4(s_red + GHC_BLOCK, lane);
-  const long long row = row0 + lane < (long long)P ? row0 + lane : (long long)P - 1;  // (lanes past the end read the last row's constants)
+  const GhrMoments mo = ghr_moments(vr, Dv, s_red, lane, wave);
+  const float m_v = mo.mean, M_v = mo.m2;
+  const long long row = t.row0 + lane < (long long)P ? t.row0 + lane : (long long)P - 1;  // (lanes past the end read the last row's constants)
   GhcRow r;
   r.fb = fold + Hd + (size_t)Hd * Dv + (size_t)(row / N) * (2 + 2 * Hd);
   const float m_e = r.fb[0], M_e = r.fb[1];
@@ -250,8 +175,8 @@ __device__ __forceinline__ GhcRow ghc_forward_tile(float* s_red, float* s_v, flo
   for (int k = wave; k < Dv; k += 4) vr[k] -= mu;
   __syncthreads();
   const float* c0 = fold;
-  ghc_linear(vr, Dv, fold + Hd, Hd, wave, [&](int j, float t) {
-    float v = fmaf(r.rstd, (t + r.fb[2 + Hd + j]) + r.dm * r.fb[2 + j], c0[j]);
+  ghr_linear(Dv, fold + Hd, Hd, wave, [&](int k) { return vr[k]; }, [&](int j, float a) {
+    float v = fmaf(r.rstd, (a + r.fb[2 + Hd + j]) + r.dm * r.fb[2 + j], c0[j]);
     v = v > 0.f ? v : (v == v ? 0.f : v);  // (a NaN stays a NaN, as torch's relu keeps it)
     s_h[lane * HP + j] = v;
   });
@@ -269,16 +194,15 @@ __global__ __launch_bounds__(GHC_BLOCK) void ghc_fwd_kernel(GhcIn in, int P, int
   float* s_red = ghc_smem;              // 2 x GHC_BLOCK
   float* s_v = s_red + 2 * GHC_BLOCK;   // GHC_ROWS x VP: the row, later the output (VP >= Hd)
   float* s_h = s_v + GHC_ROWS * VP;     // GHC_ROWS x HP
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long row0 = (long long)blockIdx.x * GHC_ROWS;
-  const int nrows = (int)((long long)P - row0 < GHC_ROWS ? (long long)P - row0 : GHC_ROWS);
-  ghc_forward_tile(s_red, s_v, s_h, VP, HP, in, P, N, De, Hd, fold, eps, row0, nrows, tid, lane, wave);
-  ghc_linear(s_h + lane * HP, Hd, W2, Hd, wave, [&](int j, float t) { s_v[lane * VP + j] = t + b2[j]; });
+  const GhrTile t = ghr_tile<GHC_ROWS>(P);
+  ghc_forward_tile(s_red, s_v, s_h, VP, HP, in, P, N, De, Hd, fold, eps, t);
+  const float* hr = s_h + t.lane * HP;
+  float* outr = s_v + t.lane * VP;
+  ghr_linear(Hd, W2, Hd, t.wave, [&](int k) { return hr[k]; }, [&](int j, float a) { outr[j] = a + b2[j]; });
   __syncthreads();
-  for (int e = tid; e < nrows * Hd; e += GHC_BLOCK) {  // the tile's contiguous run of the output
+  for (int e = t.tid; e < t.nrows * Hd; e += GHC_BLOCK) {  // the tile's contiguous run of the output
     const int r = e / Hd, c = e - r * Hd;
-    out[row0 * Hd + e] = s_v[r * VP + c];
+    out[t.row0 * Hd + e] = s_v[r * VP + c];
   }
 }
 
@@ -292,23 +216,21 @@ __global__ __launch_bounds__(GHC_BLOCK) void ghc_bwd_kernel(GhcIn in, int P, int
   float* s_h = s_v + GHC_ROWS * VP;     // GHC_ROWS x HP: h1, then d1 in place
   float* s_g = s_h + GHC_ROWS * HP;     // GHC_ROWS x HP: the cotangent
   float* s_a = s_g + GHC_ROWS * HP;     // GHC_ROWS x CP: a over the code columns, then dcode in place
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long row0 = (long long)blockIdx.x * GHC_ROWS;
-  const int nrows = (int)((long long)P - row0 < GHC_ROWS ? (long long)P - row0 : GHC_ROWS);
-  const GhcRow r = ghc_forward_tile(s_red, s_v, s_h, VP, HP, in, P, N, De, Hd, fold, eps, row0, nrows, tid, lane, wave);
-  for (int e = tid; e < GHC_ROWS * Hd; e += GHC_BLOCK) {  // rows past the end, and a null cotangent, are zeros
+  const GhrTile t = ghr_tile<GHC_ROWS>(P);
+  const int lane = t.lane, wave = t.wave;
+  const GhcRow r = ghc_forward_tile(s_red, s_v, s_h, VP, HP, in, P, N, De, Hd, fold, eps, t);
+  for (int e = t.tid; e < GHC_ROWS * Hd; e += GHC_BLOCK) {  // rows past the end, and a null cotangent, are zeros
     const int rr = e / Hd, c = e - rr * Hd;
-    s_g[rr * HP + c] = (rr < nrows && g_out) ? g_out[row0 * Hd + e] : 0.f;
+    s_g[rr * HP + c] = (rr < t.nrows && g_out) ? g_out[t.row0 * Hd + e] : 0.f;
   }
   __syncthreads();
   float* hr = s_h + lane * HP;
-  ghc_linear_t(s_g + lane * HP, Hd, W2, Hd, wave, [&](int i, float a) { hr[i] = hr[i] > 0.f ? a : 0.f; });  // h1 > 0 exactly where pre1 > 0
+  ghr_linear_t(s_g + lane * HP, Hd, W2, Hd, wave, [&](int i, float a) { hr[i] = hr[i] > 0.f ? a : 0.f; });  // h1 > 0 exactly where pre1 > 0
   __syncthreads();
   const float* vr = s_v + lane * VP;
   float* ar = s_a + lane * CP;
   float p1 = 0.f, p2 = 0.f;  // this wave's share of s1 and s2
-  ghc_linear_t(hr, Hd, fold + Hd, Dv, wave, [&](int k, float a) {
+  ghr_linear_t(hr, Hd, fold + Hd, Dv, wave, [&](int k, float a) {
     p1 += a;
     p2 = fmaf(a, r.rstd * vr[k], p2);
     if (k >= code0) ar[k - code0] = a;
@@ -322,12 +244,12 @@ __global__ __launch_bounds__(GHC_BLOCK) void ghc_bwd_kernel(GhcIn in, int P, int
   s_red[wave * GHC_ROWS + lane] = p1 + q1;
   s_red[GHC_BLOCK + wave * GHC_ROWS + lane] = fmaf(r.rstd, q2, p2);
   __syncthreads();
-  const float m1 = ghc_sum4(s_red, lane) / (float)D, m2 = ghc_sum4(s_red + GHC_BLOCK, lane) / (float)D;
+  const float m1 = ghr_sum4(s_red, lane) / (float)D, m2 = ghr_sum4(s_red + GHC_BLOCK, lane) / (float)D;
   for (int k = wave; k < Cc; k += 4) ar[k] = fmaf(-(r.rstd * vr[code0 + k]), m2, ar[k] - m1) * r.rstd;
   __syncthreads();
-  for (int i = tid; i < nrows * Cc; i += GHC_BLOCK) {
+  for (int i = t.tid; i < t.nrows * Cc; i += GHC_BLOCK) {
     const int rr = i / Cc, c = i - rr * Cc;
-    dcode[(row0 + rr) * dcode_stride + c] = s_a[rr * CP + c];
+    dcode[(t.row0 + rr) * dcode_stride + c] = s_a[rr * CP + c];
   }
 }
 
@@ -347,16 +269,6 @@ static int ghc_layout(const GhCondRows* in, GhcIn* o) {
 }
 
 static inline unsigned ghc_blocks(int P) { return (unsigned)((P + GHC_ROWS - 1) / GHC_ROWS); }
-
-// a kernel that may ask for more than 64 KB of dynamic LDS says so, once per process (sets an upper limit, enqueues nothing)
-template <class Kern>
-static void ghc_allow_lds(Kern kern, size_t lds) {
-  static bool told = false;
-  if (lds > 64 * 1024 && !told) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    told = true;
-  }
-}
 
 extern "C" int gh_cond_width(const GhCondRows* in) { return ghc_layout(in, nullptr); }
 
@@ -410,7 +322,7 @@ extern "C" int gh_cond_mlp_forward(const GhCondRows* in, int P, int N, int De, i
   const int VP = ghc_vp(Dv, Hd), HP = Hd | 1;
   const size_t lds = (size_t)(2 * GHC_BLOCK + GHC_ROWS * (VP + HP)) * sizeof(float);
   (void)hipGetLastError();
-  ghc_allow_lds(ghc_fwd_kernel, lds);
+  ghr_allow_lds<ghc_fwd_kernel>(lds);
   hipLaunchKernelGGL(ghc_fwd_kernel, dim3(ghc_blocks(P)), dim3(GHC_BLOCK), lds, (hipStream_t)hip_stream, g, P, N, De, Hd, fold,
                      params->fc2_weight, params->fc2_bias, eps, out, VP);
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
@@ -427,7 +339,7 @@ extern "C" int gh_cond_mlp_backward(const GhCondRows* in, int P, int N, int De, 
   const int VP = ghc_vp(Dv, Hd), HP = Hd | 1, CP = g.Cc | 1;
   const size_t lds = (size_t)(2 * GHC_BLOCK + GHC_ROWS * (VP + 2 * HP + CP)) * sizeof(float);
   (void)hipGetLastError();
-  ghc_allow_lds(ghc_bwd_kernel, lds);
+  ghr_allow_lds<ghc_bwd_kernel>(lds);
   hipLaunchKernelGGL(ghc_bwd_kernel, dim3(ghc_blocks(P)), dim3(GHC_BLOCK), lds, (hipStream_t)hip_stream, g, P, N, De, Hd, fold,
                      params->fc2_weight, eps, g_out, dcode, (long long)dcode_stride, VP);
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;

@@ -1,9 +1,15 @@
-// gh_rows.h — what the row-tile blocks (csrc_head/gh_head.hip, csrc_vert/gh_vert.hip) share. Internal: not part of the C-ABI.
+// gh_rows.h — what the row-tile blocks (csrc_head/gh_head.hip, csrc_vert/gh_vert.hip, csrc_cond/gh_cond.hip) share. Internal: not part
+// of the C-ABI.
 //   tile      one 4-wave workgroup per 64 rows; the rows' feature columns cross LDS at an odd pitch, so that lane = row reads its own
-//             row without a bank conflict (ghr_stage).
+//             row without a bank conflict (ghr_stage, head and vert; cond builds its rows there). ghr_tile is the prologue of the vert
+//             and cond kernels.
+//   layers    vert and cond: the LayerNorm's moments (ghr_moments), row . W^T (ghr_linear) and g . W (ghr_linear_t) for the lane's row
+//             with wave-uniform weights, the four waves' partial sums through ghr_sum4. The caller supplies how an input column is read
+//             and where a sum goes; the routines know no block.
 //   reduce    the per-workgroup partials of a backward are summed by a second launch, GHR_RED_EL elements x GHR_SEGMENTS runs per
-//             workgroup: a run is summed in workgroup order, then the runs in run order (ghr_reduce).
-// gh_pool.hip and gh_metrics.hip take ghr_align from here.
+//             workgroup: a run is summed in workgroup order, then the runs in run order (ghr_reduce; head and vert).
+//   host      ghr_allow_lds (vert, cond): more than 64 KB of dynamic LDS, told to the runtime once per kernel.
+// gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage.
 #ifndef GH_ROWS_H
 #define GH_ROWS_H
 
@@ -12,10 +18,12 @@
 #include <stdint.h>
 
 #define GHR_BLOCK 256
+#define GHR_ROWS 64      // rows per tile: lane = row
 #define GHR_SEGMENTS 16  // runs of partials (GH_HEAD_SEGMENTS, GH_VERT_SEGMENTS)
 #define GHR_RED_EL 16    // elements per workgroup of the reduction
 
 static_assert(GHR_SEGMENTS * GHR_RED_EL == GHR_BLOCK, "one thread per (run, element) of the reduction");
+static_assert(GHR_BLOCK == 4 * GHR_ROWS, "lane = row, four waves share a row's columns");
 
 static inline size_t ghr_align(size_t x) { return (x + 255) & ~(size_t)255; }  // workspace parts start on 256 bytes
 static inline bool ghr_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -65,5 +73,130 @@ __device__ __forceinline__ void ghr_reduce(int nblk, int n, Load load, Store sto
 }
 
 static inline unsigned ghr_reduce_blocks(int n) { return (unsigned)((n + GHR_RED_EL - 1) / GHR_RED_EL); }
+
+// ---- the LayerNorm-MLP row kernels (vert, cond) -----------------------------------------------------------------------------------
+// a row kernel's prologue: workgroup b works on the rows [row0, row0 + nrows) of P, R of them but for the last; `lane` is the
+// thread's row in the tile (R = 32: lanes l and l + 32 share one), `wave` is wave-uniform
+struct GhrTile {
+  int tid, lane, wave, nrows;
+  long long row0;
+};
+
+template <int R>
+__device__ __forceinline__ GhrTile ghr_tile(int P) {
+  GhrTile t;
+  t.tid = threadIdx.x;
+  t.lane = t.tid & (R - 1);
+  t.wave = __builtin_amdgcn_readfirstlane(t.tid >> 6);
+  t.row0 = (long long)blockIdx.x * R;
+  t.nrows = (int)((long long)P - t.row0 < R ? (long long)P - t.row0 : R);
+  return t;
+}
+
+// (s0 + s1) + (s2 + s3) of the four waves' partial sums of the lane's row
+__device__ __forceinline__ float ghr_sum4(const float* s_red, int lane) {
+  return (s_red[lane] + s_red[GHR_ROWS + lane]) + (s_red[2 * GHR_ROWS + lane] + s_red[3 * GHR_ROWS + lane]);
+}
+
+struct GhrMoments { float mean, m2; };  // m2: the sum of the squared deviations from the mean
+
+// the moments of the n columns of the lane's row vr: wave w sums the columns k = w mod 4 in ascending order, the four shares are added
+// by ghr_sum4. s_red is 2 x GHR_BLOCK floats (one half per pass); two barriers, so every thread of the workgroup calls it.
+__device__ __forceinline__ GhrMoments ghr_moments(const float* vr, int n, float* s_red, int lane, int wave) {
+  GhrMoments r;
+  float s = 0.f;
+  for (int k = wave; k < n; k += 4) s += vr[k];
+  s_red[wave * GHR_ROWS + lane] = s;
+  __syncthreads();
+  r.mean = ghr_sum4(s_red, lane) / (float)n;
+  float q = 0.f;
+  for (int k = wave; k < n; k += 4) {
+    const float d = vr[k] - r.mean;
+    q = fmaf(d, d, q);
+  }
+  s_red[GHR_BLOCK + wave * GHR_ROWS + lane] = q;
+  __syncthreads();
+  r.m2 = ghr_sum4(s_red + GHR_BLOCK, lane);
+  return r;
+}
+
+// emit(j, sum_k in(k) * W[j, k]) for the lane's row, W (m, n): four partial sums (k mod 4), one fmaf per term, (s0 + s1) + (s2 + s3).
+// Wave w owns j = w, w + 4, ..., three at a time: one read of the input against three fmaf with a wave-uniform weight.
+template <class In, class Emit>
+__device__ __forceinline__ void ghr_linear(int n, const float* __restrict__ W, int m, int wave, In in, Emit emit) {
+  const int n4 = n & ~3, tail = n & 3;
+  for (int j0 = wave; j0 < m; j0 += 12) {
+    const float* w[3];
+    float acc[3][4];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int j = j0 + 4 * u;
+      w[u] = W + (size_t)(j < m ? j : m - 1) * n;  // (outputs past m are computed and dropped)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[u][s] = 0.f;
+    }
+#pragma unroll 2
+    for (int k = 0; k < n4; k += 4) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const float xv = in(k + s);
+#pragma unroll
+        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][k + s], acc[u][s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {  // column n4 + s belongs to partial sum s
+      if (s < tail) {
+        const float xv = in(n4 + s);
+#pragma unroll
+        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][n4 + s], acc[u][s]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int j = j0 + 4 * u;
+      if (j < m) emit(j, (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]));
+    }
+  }
+}
+
+// emit(k, sum_i gr[i] * W[i, k]) for the lane's row, W (m, ncols): one chain of fmaf in ascending i; wave w owns k = 16t + 4w .. 16t + 4w + 3
+template <class Emit>
+__device__ __forceinline__ void ghr_linear_t(const float* gr, int m, const float* __restrict__ W, int ncols, int wave, Emit emit) {
+  for (int k0 = 4 * wave; k0 < ncols; k0 += 16) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (k0 + 4 <= ncols) {
+#pragma unroll 2
+      for (int i = 0; i < m; ++i) {
+        const float g = gr[i];
+        const float* wr = W + (size_t)i * ncols + k0;
+        a0 = fmaf(g, wr[0], a0); a1 = fmaf(g, wr[1], a1); a2 = fmaf(g, wr[2], a2); a3 = fmaf(g, wr[3], a3);
+      }
+    } else {  // the last, partial block: columns past the end repeat the last one and are dropped
+      const int c1 = k0 + 1 < ncols ? 1 : 0, c2 = k0 + 2 < ncols ? 2 : c1;
+      for (int i = 0; i < m; ++i) {
+        const float g = gr[i];
+        const float* wr = W + (size_t)i * ncols + k0;
+        a0 = fmaf(g, wr[0], a0); a1 = fmaf(g, wr[c1], a1); a2 = fmaf(g, wr[c2], a2);
+      }
+    }
+    emit(k0, a0);
+    if (k0 + 1 < ncols) emit(k0 + 1, a1);
+    if (k0 + 2 < ncols) emit(k0 + 2, a2);
+    if (k0 + 3 < ncols) emit(k0 + 3, a3);
+  }
+}
+
+// A kernel that may ask for more than 64 KB of dynamic LDS says so, once per process, where the runtime wants to be told (the call sets
+// an upper limit, a CU's 160 KiB, and enqueues nothing). The flag belongs to the kernel, not to its function type: kernels of equal
+// signature, such as the instantiations of one template, are told each on its own first launch.
+template <auto Kern>
+static void ghr_allow_lds(size_t lds) {
+  static bool told = false;
+  if (lds > 64 * 1024 && !told) {
+    (void)hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    told = true;
+  }
+}
 
 #endif

@@ -3,10 +3,10 @@
 //   tile      one 4-wave workgroup per GH_VERT_ROWS = 64 rows, lane = row, wave-uniform weights through the scalar cache. The rows'
 //             features and positions are loaded coalesced (16-byte loads where x allows) into LDS at an odd pitch (D | 1), so that a
 //             lane reads its own row without a bank conflict; the concatenation exists there only.
-//   forward   LayerNorm in place (wave w sums the columns k = w mod 4), then fc1 / fc2 / fc through ghv_linear: wave w owns the
+//   forward   LayerNorm in place (wave w sums the columns k = w mod 4), then fc1 / fc2 / fc through ghr_linear: wave w owns the
 //             outputs w, w + 4, ..., three at a time, one LDS read of the input against three fmaf with an SGPR operand.
 //   backward  the same forward with the normalised row kept un-scaled (the affine is applied on the fly), then the three layers
-//             backwards through ghv_linear_t: wave w owns the inputs 16t + 4w .. + 3, one LDS read of a gradient against four fmaf;
+//             backwards through ghr_linear_t: wave w owns the inputs 16t + 4w .. + 3, one LDS read of a gradient against four fmaf;
 //             the LayerNorm's backward in place; rows leave as coalesced runs. With parameter gradients: the tile's 64 rows are
 //             summed in ascending row order into one partial per workgroup; a second launch adds the partials in a fixed order.
 // No atomics; every float sum has a fixed order that depends on (Cf, K) — and, for parameter gradients, on P — alone.
@@ -18,7 +18,7 @@
 #define GHV_OP 3        // pitch of the output tile (K <= 3)
 #define GHV_LDS_MAX (128 * 1024)  // the most LDS a workgroup of the backward takes (a CU has 160 KiB)
 
-static_assert(GHV_ROWS == 64 && GHV_BLOCK == 4 * GHV_ROWS, "lane = row, four waves share a row's columns");
+static_assert(GHV_ROWS == GHR_ROWS, "the shared row routines' tile: lane = row, four waves share a row's columns");
 static_assert(GH_VERT_SEGMENTS == GHR_SEGMENTS, "the header documents the shared reduction's run count");
 
 // the tile's R rows of (x, pts) -> s_z[row * ZP + col]; rows past the end are zeros
@@ -31,122 +31,42 @@ __device__ __forceinline__ void ghv_stage(float* s_z, int ZP, const float* __res
   }
 }
 
-// out[j] = act(b[j] + sum_k in[k] * W[j, k]) for the lane's row; wave w owns j = w, w + 4, ...; AFFINE: in[k] is gamma[k] * s_in[k] + beta[k]
-template <bool RELU, bool AFFINE>
-__device__ __forceinline__ void ghv_linear(const float* s_in, int ip, int n, const float* __restrict__ W, const float* __restrict__ b,
-                                           int m, float* s_out, int op, int lane, int wave, const float* __restrict__ gamma,
-                                           const float* __restrict__ beta) {
-  const float* xr = s_in + lane * ip;
-  const int n4 = n & ~3, tail = n & 3;
-  for (int j0 = wave; j0 < m; j0 += 12) {
-    const float* w[3];
-    float acc[3][4];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int j = j0 + 4 * u;
-      w[u] = W + (size_t)(j < m ? j : m - 1) * n;  // (outputs past m are computed and dropped)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) acc[u][s] = 0.f;
-    }
-#pragma unroll 2
-    for (int k = 0; k < n4; k += 4) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float xv = xr[k + s];
-        if (AFFINE) xv = fmaf(xv, gamma[k + s], beta[k + s]);
-#pragma unroll
-        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][k + s], acc[u][s]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {  // column n4 + s belongs to partial sum s
-      if (s < tail) {
-        float xv = xr[n4 + s];
-        if (AFFINE) xv = fmaf(xv, gamma[n4 + s], beta[n4 + s]);
-#pragma unroll
-        for (int u = 0; u < 3; ++u) acc[u][s] = fmaf(xv, w[u][n4 + s], acc[u][s]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int j = j0 + 4 * u;
-      if (j < m) {
-        float v = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) + b[j];
-        if (RELU) v = v > 0.f ? v : (v == v ? 0.f : v);  // (a NaN stays a NaN, as torch's relu keeps it)
-        s_out[lane * op + j] = v;
-      }
-    }
-  }
+// the epilogue of a layer for ghr_linear: out_row[j] = act(sum + b[j])
+template <bool RELU>
+__device__ __forceinline__ auto ghv_store(float* out_row, const float* __restrict__ b) {
+  return [=](int j, float t) {
+    float v = t + b[j];
+    if (RELU) v = v > 0.f ? v : (v == v ? 0.f : v);  // (a NaN stays a NaN, as torch's relu keeps it)
+    out_row[j] = v;
+  };
 }
 
-// emit(k, sum_i g[i] * W[i, k]) for the lane's row, one chain of fmaf in ascending i; wave w owns k = 16t + 4w .. 16t + 4w + 3
-template <class F>
-__device__ __forceinline__ void ghv_linear_t(const float* s_g, int gp, int m, const float* __restrict__ W, int ncols, int lane, int wave,
-                                             F emit) {
-  const float* gr = s_g + lane * gp;
-  for (int k0 = 4 * wave; k0 < ncols; k0 += 16) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (k0 + 4 <= ncols) {
-#pragma unroll 2
-      for (int i = 0; i < m; ++i) {
-        const float g = gr[i];
-        const float* wr = W + (size_t)i * ncols + k0;
-        a0 = fmaf(g, wr[0], a0); a1 = fmaf(g, wr[1], a1); a2 = fmaf(g, wr[2], a2); a3 = fmaf(g, wr[3], a3);
-      }
-    } else {  // the last, partial block: columns past the end repeat the last one and are dropped
-      const int c1 = k0 + 1 < ncols ? 1 : 0, c2 = k0 + 2 < ncols ? 2 : c1;
-      for (int i = 0; i < m; ++i) {
-        const float g = gr[i];
-        const float* wr = W + (size_t)i * ncols + k0;
-        a0 = fmaf(g, wr[0], a0); a1 = fmaf(g, wr[c1], a1); a2 = fmaf(g, wr[c2], a2);
-      }
-    }
-    emit(k0, a0);
-    if (k0 + 1 < ncols) emit(k0 + 1, a1);
-    if (k0 + 2 < ncols) emit(k0 + 2, a2);
-    if (k0 + 3 < ncols) emit(k0 + 3, a3);
-  }
-}
-
-// (s0 + s1) + (s2 + s3) of the four waves' partial sums of the lane's row
-__device__ __forceinline__ float ghv_sum4(const float* s_red, int lane) {
-  return (s_red[lane] + s_red[GHV_ROWS + lane]) + (s_red[2 * GHV_ROWS + lane] + s_red[3 * GHV_ROWS + lane]);
-}
-
-// stage, LayerNorm in place, fc1, fc2, fc. s_z is left holding gamma * xhat + beta (AFFINE_LATER false) or xhat (true); returns rstd.
-// s_h2 may alias s_z when AFFINE_LATER is false (the normalised row is dead once fc1 is through).
+// stage, LayerNorm in place, fc1, fc2, fc. s_z is left holding gamma * xhat + beta (AFFINE_LATER false) or xhat (true), and fc1 then
+// applies the affine on the fly; returns rstd. s_h2 may alias s_z when AFFINE_LATER is false (the normalised row is dead once fc1 is
+// through).
 template <bool AFFINE_LATER>
 __device__ __forceinline__ float ghv_forward_tile(float* s_red, float* s_z, float* s_h1, float* s_h2, float* s_o, int ZP, int HP,
                                                   const float* __restrict__ x, long long x_stride, const float* __restrict__ pts,
-                                                  long long row0, int R, int nrows, int Cf, int Hd, int K, float eps,
-                                                  GhVertParams p, int vec_x, int tid, int lane, int wave) {
-  const int D = Cf + 3;
-  ghv_stage(s_z, ZP, x, x_stride, pts, row0, R, nrows, Cf, vec_x, tid);
+                                                  const GhrTile& t, int R, int Cf, int Hd, int K, float eps, GhVertParams p, int vec_x) {
+  const int D = Cf + 3, lane = t.lane, wave = t.wave;
+  ghv_stage(s_z, ZP, x, x_stride, pts, t.row0, R, t.nrows, Cf, vec_x, t.tid);
   __syncthreads();
   float* zr = s_z + lane * ZP;
-  float s = 0.f;
-  for (int k = wave; k < D; k += 4) s += zr[k];
-  s_red[wave * GHV_ROWS + lane] = s;
-  __syncthreads();
-  const float mean = ghv_sum4(s_red, lane) / (float)D;
-  float q = 0.f;
+  const GhrMoments mo = ghr_moments(zr, D, s_red, lane, wave);
+  const float rstd = 1.0f / sqrtf(mo.m2 / (float)D + eps);
   for (int k = wave; k < D; k += 4) {
-    const float d = zr[k] - mean;
-    q = fmaf(d, d, q);
-  }
-  s_red[GHV_BLOCK + wave * GHV_ROWS + lane] = q;
-  __syncthreads();
-  const float rstd = 1.0f / sqrtf(ghv_sum4(s_red + GHV_BLOCK, lane) / (float)D + eps);
-  for (int k = wave; k < D; k += 4) {
-    const float xh = (zr[k] - mean) * rstd;
+    const float xh = (zr[k] - mo.mean) * rstd;
     zr[k] = AFFINE_LATER ? xh : fmaf(xh, p.ln_weight[k], p.ln_bias[k]);
   }
   __syncthreads();
-  ghv_linear<true, AFFINE_LATER>(s_z, ZP, D, p.fc1_weight, p.fc1_bias, Hd, s_h1, HP, lane, wave, p.ln_weight, p.ln_bias);
+  ghr_linear(D, p.fc1_weight, Hd, wave, [&](int k) { return AFFINE_LATER ? fmaf(zr[k], p.ln_weight[k], p.ln_bias[k]) : zr[k]; },
+             ghv_store<true>(s_h1 + lane * HP, p.fc1_bias));
   __syncthreads();
-  ghv_linear<false, false>(s_h1, HP, Hd, p.fc2_weight, p.fc2_bias, Hd, s_h2, HP, lane, wave, nullptr, nullptr);
+  const float* h1 = s_h1 + lane * HP;
+  ghr_linear(Hd, p.fc2_weight, Hd, wave, [&](int k) { return h1[k]; }, ghv_store<false>(s_h2 + lane * HP, p.fc2_bias));
   __syncthreads();
-  ghv_linear<false, false>(s_h2, HP, Hd, p.fc_weight, p.fc_bias, K, s_o, GHV_OP, lane, wave, nullptr, nullptr);
+  const float* h2 = s_h2 + lane * HP;
+  ghr_linear(Hd, p.fc_weight, K, wave, [&](int k) { return h2[k]; }, ghv_store<false>(s_o + lane * GHV_OP, p.fc_bias));
   __syncthreads();
   return rstd;
 }
@@ -161,15 +81,12 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_fwd_kernel(const float* __restr
   float* s_z = s_red + 2 * GHV_BLOCK;         // GHV_ROWS x ZP; later the second hidden layer (HP < ZP)
   float* s_h1 = s_z + GHV_ROWS * ZP;          // GHV_ROWS x HP
   float* s_o = s_h1 + GHV_ROWS * HP;          // GHV_ROWS x GHV_OP
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long row0 = (long long)blockIdx.x * GHV_ROWS;
-  const int nrows = (int)((long long)P - row0 < GHV_ROWS ? (long long)P - row0 : GHV_ROWS);
-  ghv_forward_tile<false>(s_red, s_z, s_h1, s_z, s_o, ZP, HP, x, x_stride, pts, row0, GHV_ROWS, nrows, Cf, Hd, K, eps, p, vec_x, tid, lane, wave);
-  for (int e = tid; e < nrows * K; e += GHV_BLOCK) {  // the tile's contiguous run of the output
+  const GhrTile t = ghr_tile<GHV_ROWS>(P);
+  ghv_forward_tile<false>(s_red, s_z, s_h1, s_z, s_o, ZP, HP, x, x_stride, pts, t, GHV_ROWS, Cf, Hd, K, eps, p, vec_x);
+  for (int e = t.tid; e < t.nrows * K; e += GHV_BLOCK) {  // the tile's contiguous run of the output
     const int r = e / K, c = e - r * K;
     const float v = s_o[r * GHV_OP + c];
-    out[row0 * K + e] = act == GH_VERT_ACT_SIGMOID ? ghr_sigmoid(v) : pts[row0 * 3 + e] + tanhf(v) * radius;
+    out[t.row0 * K + e] = act == GH_VERT_ACT_SIGMOID ? ghr_sigmoid(v) : pts[t.row0 * 3 + e] + tanhf(v) * radius;
   }
 }
 
@@ -229,19 +146,16 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
   float* s_gh2 = s_h2 + R * HP;
   float* s_gp1 = s_gh2 + R * HP;
   float* s_o = s_gp1 + R * HP;                 // R x GHV_OP: o, then its gradient
-  const int tid = threadIdx.x, lane = tid & (R - 1);  // the lane's row
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long row0 = (long long)blockIdx.x * R;
-  const int nrows = (int)((long long)P - row0 < R ? (long long)P - row0 : R);
-  const float rstd = ghv_forward_tile<true>(s_red, s_z, s_h1, s_h2, s_o, ZP, HP, x, x_stride, pts, row0, R, nrows, Cf, Hd, K, eps, p,
-                                            vec_x, tid, lane, wave);
+  const GhrTile t = ghr_tile<R>(P);
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const float rstd = ghv_forward_tile<true>(s_red, s_z, s_h1, s_h2, s_o, ZP, HP, x, x_stride, pts, t, R, Cf, Hd, K, eps, p, vec_x);
 
   // ---- the gradient of o; rows past the end are zeros (they enter the tile's sums of the parameter gradients) ----
   for (int e = tid; e < R * K; e += GHV_BLOCK) {
     const int r = e / K, c = e - r * K;
     float go = 0.f;
-    if (r < nrows && g_out) {
-      const float g = g_out[row0 * K + e], v = s_o[r * GHV_OP + c];
+    if (r < t.nrows && g_out) {
+      const float g = g_out[t.row0 * K + e], v = s_o[r * GHV_OP + c];
       if (act == GH_VERT_ACT_SIGMOID) {
         const float s = ghr_sigmoid(v);
         go = (g * (1.0f - s)) * s;
@@ -253,15 +167,15 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
     s_o[r * GHV_OP + c] = go;
   }
   __syncthreads();
-  ghv_linear_t(s_o, GHV_OP, K, p.fc_weight, Hd, lane, wave, [&](int j, float a) { s_gh2[lane * HP + j] = a; });
+  ghr_linear_t(s_o + lane * GHV_OP, K, p.fc_weight, Hd, wave, [&](int j, float a) { s_gh2[lane * HP + j] = a; });
   __syncthreads();
-  ghv_linear_t(s_gh2, HP, Hd, p.fc2_weight, Hd, lane, wave,
+  ghr_linear_t(s_gh2 + lane * HP, Hd, p.fc2_weight, Hd, wave,
                [&](int i, float a) { s_gp1[lane * HP + i] = s_h1[lane * HP + i] > 0.f ? a : 0.f; });  // h1 > 0 exactly where pre1 > 0
   __syncthreads();
   const float* zr = s_z + lane * ZP;
   float* gr = s_gz + lane * ZP;
   float p1 = 0.f, p2 = 0.f;  // this wave's share of sum_k gxhat[k] and of sum_k gxhat[k] * xhat[k], gxhat = gamma * gzn
-  ghv_linear_t(s_gp1, HP, Hd, p.fc1_weight, D, lane, wave, [&](int k, float a) {
+  ghr_linear_t(s_gp1 + lane * HP, Hd, p.fc1_weight, D, wave, [&](int k, float a) {
     gr[k] = a;
     const float gxh = a * p.ln_weight[k];
     p1 += gxh;
@@ -294,7 +208,7 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
   }
 
   // ---- the LayerNorm's backward in place: gz = rstd * ((gxhat - mean(gxhat)) - xhat * mean(gxhat * xhat)) ----
-  const float m1 = ghv_sum4(s_red, lane) / (float)D, m2 = ghv_sum4(s_red + GHV_BLOCK, lane) / (float)D;
+  const float m1 = ghr_sum4(s_red, lane) / (float)D, m2 = ghr_sum4(s_red + GHV_BLOCK, lane) / (float)D;
   for (int k0 = 4 * wave; k0 < D; k0 += 16) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -303,14 +217,14 @@ __global__ __launch_bounds__(GHV_BLOCK) void ghv_bwd_kernel(const float* __restr
     }
   }
   __syncthreads();
-  for (int i = tid; i < nrows * Cf; i += GHV_BLOCK) {
+  for (int i = tid; i < t.nrows * Cf; i += GHV_BLOCK) {
     const int r = i / Cf, c = i - r * Cf;
-    grad_x[(row0 + r) * gx_stride + c] = s_gz[r * ZP + c];
+    grad_x[(t.row0 + r) * gx_stride + c] = s_gz[r * ZP + c];
   }
   if (grad_pts) {
-    for (int i = tid; i < nrows * 3; i += GHV_BLOCK) {
+    for (int i = tid; i < t.nrows * 3; i += GHV_BLOCK) {
       const int r = i / 3, c = i - 3 * r;
-      grad_pts[row0 * 3 + i] = s_gz[r * ZP + Cf + c];
+      grad_pts[t.row0 * 3 + i] = s_gz[r * ZP + Cf + c];
     }
   }
 }
@@ -352,17 +266,6 @@ static int ghv_check(int P, int Cf, const GhVertParams* p, const GhVertDesc* d) 
   return GH_OK;
 }
 
-// a kernel that may ask for more than 64 KB of dynamic LDS says so, once per process, where the runtime wants to be told (the call
-// sets an upper limit — the most these kernels ever use, at Cf = GH_VERT_MAX_CF — and enqueues nothing)
-template <class Kern>
-static void ghv_allow_lds(Kern kern, size_t lds) {
-  static bool told = false;
-  if (lds > 64 * 1024 && !told) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    told = true;
-  }
-}
-
 extern "C" size_t gh_vert_workspace_bytes(int P, int D, int Hd, int K) {
   if (P < 1 || D < 4 || D > GH_VERT_MAX_CF + 3 || Hd != D / 4 || (K != 1 && K != 3)) return 0;
   const int rows = ghv_bwd_rows(D);
@@ -380,7 +283,7 @@ extern "C" int gh_vert_forward(const float* x, int64_t x_stride, const float* pt
   const size_t lds = (size_t)(2 * GHV_BLOCK + GHV_ROWS * (ZP + HP + GHV_OP)) * sizeof(float);
   hipStream_t s = (hipStream_t)hip_stream;
   (void)hipGetLastError();
-  ghv_allow_lds(ghv_fwd_kernel, lds);
+  ghr_allow_lds<ghv_fwd_kernel>(lds);
   hipLaunchKernelGGL(ghv_fwd_kernel, dim3((unsigned)ghv_blocks(P)), dim3(GHV_BLOCK), lds, s, x, (long long)x_stride, pts, P, Cf, *params,
                      (int)desc->K, desc->act, desc->radius, desc->eps, out, vec_x);
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
@@ -410,7 +313,7 @@ extern "C" int gh_vert_backward(const float* x, int64_t x_stride, const float* p
   (void)hipGetLastError();
 #define GHV_BWD(WG, RB)                                                                                                              \
   do {                                                                                                                              \
-    ghv_allow_lds(ghv_bwd_kernel<WG, RB>, lds);                                                                                     \
+    ghr_allow_lds<ghv_bwd_kernel<WG, RB>>(lds);                                                                                     \
     hipLaunchKernelGGL((ghv_bwd_kernel<WG, RB>), grid, block, lds, s, x, (long long)x_stride, pts, P, Cf, *params, K, desc->act,   \
                        desc->radius, desc->eps, g_out, grad_x, (long long)gx_stride, grad_pts, (float*)workspace, off, vec_x);     \
   } while (0)

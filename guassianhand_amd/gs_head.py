@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import check_f32, launch, lib, ptr, row_stride, rows, workspace
+from ._call import check_f32, check_ops, cotangent, launch, lib, ptr, row_stride, rows, workspace
 from .renderer import GaussianModel, gs_activations
 
 FIELDS = ("xyz", "scaling", "rotation", "opacity", "shs")          # the order of the concatenated rows (gh_head.h)
@@ -142,7 +142,7 @@ class _GsHeadFn(torch.autograd.Function):
             if need_w:
                 gw.zero_(), gb.zero_()
         else:
-            gs = [None if g is None else g.float().contiguous() for g in (g_xyz, g_scaling, g_rotation, g_opacity, g_shs)]
+            gs = [cotangent(g) for g in (g_xyz, g_scaling, g_rotation, g_opacity, g_shs)]
             nbytes = int(lib().gh_head_workspace_bytes(P, Cin, O)) if need_w else 0
             ws = workspace(nbytes, dev) if need_w else None
             launch("gh_head_backward", dev, ptr(raw), ptr(x), row_stride(x), P, Cin, ptr(weight), C.byref(_desc(*ctx.cfg)),
@@ -159,8 +159,7 @@ def gs_head(x: torch.Tensor, pts: torch.Tensor, weight: torch.Tensor, bias: torc
     rotation (P,4), scaling (P,3), shs (P, shs_width / 3, 3)): GSLayer.forward with the five heads concatenated in FIELDS order.
     The keyword defaults are GSLayer.Config's. ops="torch" runs the plain-torch restatement on x's device instead of the kernels;
     CPU tensors always take it."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     _check(x, pts, weight, bias, shs_width, use_rgb, clip_scaling)
     cfg = (int(shs_width), bool(use_rgb), bool(xyz_offset), bool(restrict_offset), None if clip_scaling is None else float(clip_scaling))
     if ops == "torch" or not x.is_cuda:

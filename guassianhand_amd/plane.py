@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import launch, lib, ptr, workspace
+from ._call import check_ops, launch, lib, ptr, workspace
 
 MAX_TEXELS = _abi.GH_POOL_MAX_CELLS
 
@@ -160,8 +160,7 @@ def plane_sample(planes: torch.Tensor, uv: torch.Tensor, *, index: Union[None, P
     its batch element's plane, zeros outside the map. Differentiable with respect to `planes` (and, through torch, to `uv`).
     index: the PlaneIndex of uv[b] on (Hp, Wp) — one, or a sequence of B — when the caller holds it; otherwise built when `planes`
     needs a gradient and kept for the same `uv` tensor. ops="torch" runs the plain-torch restatement on the tensors' device."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     if planes.dim() == 5:
         if planes.shape[1] != 1:
             raise ValueError(f"planes: expected (B, 1, C, Hp, Wp), got {tuple(planes.shape)}")

@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import _abi
-from ._call import launch, lib, ptr, row_stride, rows, workspace
+from ._call import check_ops, launch, lib, ptr, row_stride, rows, workspace
 from .cond import PointRows
 
 _REDUCE = {"max": _abi.GH_POOL_MAX, "mean": _abi.GH_POOL_MEAN}
@@ -365,8 +365,7 @@ def pointnet_forward(self, p, ops: Optional[str] = None) -> torch.Tensor:
     `p` may be a cond.PointRows standing for the (B,T,D) concatenation: the cell index then comes from its uv columns and the first
     layer from PointRows.linear(self.fc_pos); the concatenation is not built."""
     ops = ops or getattr(self, "pool_ops", "fused")
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     given = isinstance(p, PointRows)
     if not given and p.dim() != 3:
         raise ValueError(f"p: expected (B, T, D), got {tuple(p.shape)}")

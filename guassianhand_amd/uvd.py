@@ -35,7 +35,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _abi
-from ._call import launch, lib, ptr, workspace
+from ._call import check_ops, launch, lib, ptr, workspace
 
 MAX_SPLIT = _abi.GH_UVD_MAX_SPLIT
 _REF_PAIRS = 1 << 22                     # point-face pairs per chunk of the restatement: (n, F) temporaries of 16 MB in float32
@@ -210,8 +210,7 @@ def closest_uv(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, f
     contract of include/gh_uvd.h. split: the number of face chunks searched side by side, 0 for the library's choice; the outputs do
     not depend on it. ops="torch" runs the plain-torch restatement on the tensors' device. Differentiable with respect to points,
     verts and face_uv through the winning face (module docstring)."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     if not 0 <= int(split) <= MAX_SPLIT:
         raise ValueError(f"split must lie in [0, {MAX_SPLIT}], got {split}")
     _check(points, verts, faces, face_uv)

@@ -34,7 +34,8 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import check_f32, launch, lib, ptr, row_stride, rows, struct, workspace
+from ._call import check_f32, check_ops, cotangent, launch, lib, ptr, row_stride, rows, struct, workspace
+from ._mlp_block import _MLPBlock, block_params, dropout_live, init_linears
 
 PARAMS = _abi.VERT_PARAMS                                        # the order of `params` (GhVertParams)
 ACTS = {"sigmoid": _abi.GH_VERT_ACT_SIGMOID, "tanh_offset": _abi.GH_VERT_ACT_TANH_OFFSET}
@@ -129,7 +130,7 @@ class _VertBlockFn(torch.autograd.Function):
                 for g in gparams:
                     g.zero_()
         else:
-            g = None if g_out is None else g_out.float().contiguous()
+            g = cotangent(g_out)
             nbytes = int(lib().gh_vert_workspace_bytes(P, D, Hd, K)) if need_w else 0
             ws = workspace(nbytes, dev) if need_w else None
             desc = _abi.GhVertDesc(K, ACTS[act], float(radius), float(eps))
@@ -146,8 +147,7 @@ def vert_block(x: torch.Tensor, pts: torch.Tensor, params: Sequence[torch.Tensor
     """x (P,Cf), pts (P,3), params in PARAMS order, all float32 -> (P,K): sigmoid(mlp(cat(x, pts))) for act="sigmoid", or
     pts.detach() + tanh(mlp(cat(x, pts))) * radius for act="tanh_offset" (K = 3). ops="torch" runs the plain-torch restatement on x's
     device instead of the kernels; CPU tensors always take it."""
-    if ops not in ("fused", "torch"):
-        raise ValueError(f"ops must be 'fused' or 'torch', got {ops!r}")
+    check_ops(ops)
     _check(x, pts, params, act, eps)
     if ops == "torch" or not x.is_cuda:
         return _vert_block_ref(x, pts, list(params), act=act, radius=float(radius), eps=float(eps))
@@ -156,12 +156,7 @@ def vert_block(x: torch.Tensor, pts: torch.Tensor, params: Sequence[torch.Tensor
 
 # ---- the modules -----------------------------------------------------------------------------------------------------------------
 def _module_params(self):
-    ff = self.ff
-    return [ff.layer_norm.weight, ff.layer_norm.bias, ff.fc1.weight, ff.fc1.bias, ff.fc2.weight, ff.fc2.bias, self.fc.weight, self.fc.bias]
-
-
-def _dropout_active(self) -> bool:
-    return bool(self.training) and any(float(getattr(d, "p", 0.0)) > 0 for d in (self.ff.dropout1, self.ff.dropout2))
+    return block_params(self.ff) + [self.fc.weight, self.fc.bias]
 
 
 def vert_module_forward(self, verts_f: torch.Tensor, verts_position: torch.Tensor, act: str, ops: Optional[str] = None) -> torch.Tensor:
@@ -177,21 +172,6 @@ def vert_module_forward(self, verts_f: torch.Tensor, verts_position: torch.Tenso
     return out.reshape(*lead, out.shape[-1])
 
 
-class _MLPBlock(nn.Module):
-    """The reference's MLP_block (verts_refinement.py:16-32): the sub-module names are its state-dict keys."""
-
-    def __init__(self, in_dim: int, hid_dim: int, dropout: float = 0.1):
-        super().__init__()
-        self.layer_norm = nn.LayerNorm(in_dim, eps=1e-6)
-        self.fc1 = nn.Linear(in_dim, hid_dim)
-        self.fc2 = nn.Linear(hid_dim, hid_dim)
-        self.dropout1 = nn.Dropout(dropout)
-        self.dropout2 = nn.Dropout(dropout)
-
-    def forward(self, x):
-        return self.dropout2(self.fc2(self.dropout1(F.relu(self.fc1(self.layer_norm(x))))))
-
-
 class _VertModule(nn.Module):
     ACT, K = "sigmoid", 1
 
@@ -203,10 +183,7 @@ class _VertModule(nn.Module):
         D = self.verts_f_dim + 3
         self.ff = _MLPBlock(D, D // 4)
         self.fc = nn.Linear(D // 4, self.K)
-        for m in self.modules():                                   # weights_init (verts_refinement.py:5-13)
-            if isinstance(m, nn.Linear):
-                nn.init.xavier_uniform_(m.weight)
-                nn.init.constant_(m.bias, 0.0)
+        init_linears(self)
 
     def _torch_forward(self, verts_f, verts_position):
         """The reference's forward, layer by layer (dropout included): the train-mode path."""
@@ -218,7 +195,7 @@ class _VertModule(nn.Module):
         return verts_position.detach() + torch.tanh(o) * self.radius
 
     def forward(self, verts_f, verts_position):
-        if _dropout_active(self):
+        if dropout_live(self, self.ff):
             return self._torch_forward(verts_f, verts_position)
         return vert_module_forward(self, verts_f, verts_position, self.ACT)
 
@@ -248,7 +225,7 @@ def fused_vert_cls(base):
     The activation follows the head: an `fc` with one output is the gate, with three the refinement."""
     if base not in _fused_cls:
         def forward(self, verts_f, verts_position):
-            if _dropout_active(self):
+            if dropout_live(self, self.ff):
                 return base.forward(self, verts_f, verts_position)
             return vert_module_forward(self, verts_f, verts_position, "sigmoid" if self.fc.out_features == 1 else "tanh_offset")
 
