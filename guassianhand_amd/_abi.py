@@ -398,11 +398,36 @@ def declare_cond(lib: C.CDLL) -> None:
                                          C.c_int64, C.c_void_p]
 
 
+# ---- include/gh_res.h: the encoders' ResNet blocks, pooled half per cell (a header of its own, as gh_cond.h is) ----
+GH_RES_ROWS = 128
+GH_RES_MAX_H = 128
+
+RES_SYMBOLS = ("gh_res_forward", "gh_res_backward", "gh_res_cell_sum", "gh_res_cell_max", "gh_res_cell_max_backward")
+
+
+def declare_res(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_res.h declares."""
+    V, I, L = C.c_void_p, C.c_int, C.c_int64
+    lib.gh_res_forward.restype = C.c_int
+    lib.gh_res_forward.argtypes = [V, L, I, I, I, V, V, I, V, V, L, V, L, V, V, L, V, V]
+    lib.gh_res_backward.restype = C.c_int
+    lib.gh_res_backward.argtypes = [V, L, V, L, I, I, I, V, V, L, V, L, V, V, L, V, V]
+    lib.gh_res_cell_sum.restype = C.c_int
+    lib.gh_res_cell_sum.argtypes = [V, L, I, I, I, V, V, I, V, V]
+    lib.gh_res_cell_max.restype = C.c_int
+    lib.gh_res_cell_max.argtypes = [V, L, I, I, I, V, V, V, V, V]
+    lib.gh_res_cell_max_backward.restype = C.c_int
+    lib.gh_res_cell_max_backward.argtypes = [V, V, I, I, I, V, L, V]
+
+
+bind_res = declare_res          # for a caller that loads the library itself and binds this header alone
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the nine headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond):
+    """Attach argtypes/restypes for every symbol of the ten headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res):
         one(lib)

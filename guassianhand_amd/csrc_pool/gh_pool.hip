@@ -108,42 +108,6 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_scatter_kernel(const void* __re
   if (pos >= 0 && pos < T) order[pos] = p;
 }
 
-// ---- walking a run of `order` -------------------------------------------------------------------------------------------
-// Calls f(point) for order[lo .. hi) in ascending position, 64 list entries fetched by one coalesced load and handed out by
-// v_readlane, four rows per step so that four loads are in flight. lo, hi are wave-uniform.
-template <typename Load, typename Use>
-__device__ __forceinline__ void ghp_walk(const int* __restrict__ order, int lo, int hi, Load load, Use use) {
-  const int lane = threadIdx.x & 63;
-  for (int j0 = lo; j0 < hi; j0 += 64) {
-    const int m = min(64, hi - j0);
-    const int mine = lane < m ? order[j0 + lane] : 0;
-    int k = 0;
-    for (; k + 4 <= m; k += 4) {
-      const int p0 = __builtin_amdgcn_readlane(mine, k), p1 = __builtin_amdgcn_readlane(mine, k + 1);
-      const int p2 = __builtin_amdgcn_readlane(mine, k + 2), p3 = __builtin_amdgcn_readlane(mine, k + 3);
-      const float v0 = load(p0), v1 = load(p1), v2 = load(p2), v3 = load(p3);
-      use(p0, v0); use(p1, v1); use(p2, v2); use(p3, v3);
-    }
-    for (; k < m; ++k) {
-      const int p = __builtin_amdgcn_readlane(mine, k);
-      use(p, load(p));
-    }
-  }
-}
-
-// the same walk for a pass that only writes
-template <typename Store>
-__device__ __forceinline__ void ghp_walk_store(const int* __restrict__ order, int lo, int hi, Store store) {
-  const int lane = threadIdx.x & 63;
-  for (int j0 = lo; j0 < hi; j0 += 64) {
-    const int m = min(64, hi - j0);
-    const int mine = lane < m ? order[j0 + lane] : 0;
-    for (int k = 0; k < m; ++k) store(__builtin_amdgcn_readlane(mine, k));
-  }
-}
-
-__device__ __forceinline__ int ghp_part(int a, int n, int w) { return a + (int)((long long)n * w / GHP_WAVES); }
-
 // ---- pool forward ---------------------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_fwd_kernel(const float* __restrict__ x, int xs, int T, int C, int n_cells,
@@ -156,17 +120,17 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_fwd_kernel(const float* __
   const bool on = ch < C;
   const int a = cell_start[cell], b = cell == n_cells ? T : cell_start[cell + 1], n = b - a;
   if (cell == n_cells) {                             // points without a cell: zeros
-    ghp_walk_store(order, ghp_part(a, n, w), ghp_part(a, n, w + 1), [&](int p) { if (on) out[(size_t)p * os + ch] = 0.0f; });
+    ghr_walk_store(order, ghr_part(a, n, w), ghr_part(a, n, w + 1), [&](int p) { if (on) out[(size_t)p * os + ch] = 0.0f; });
     return;
   }
   if (n <= 0) {
     if (MODE == GH_POOL_MAX && w == 0 && on) argmax[(size_t)cell * C + ch] = T;
     return;
   }
-  const int lo = ghp_part(a, n, w), hi = ghp_part(a, n, w + 1);
+  const int lo = ghr_part(a, n, w), hi = ghr_part(a, n, w + 1);
   float acc = 0.0f;
   int arg = T;
-  ghp_walk(order, lo, hi, [&](int p) { return on ? x[(size_t)p * xs + ch] : 0.0f; },
+  ghr_walk(order, lo, hi, [&](int p) { return on ? x[(size_t)p * xs + ch] : 0.0f; },
            [&](int p, float v) {
              if (MODE == GH_POOL_MAX) {
                // strict: the first of equal values stays. v == v: a NaN is never taken, wherever it sits, so a quarter (and a
@@ -193,7 +157,7 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_fwd_kernel(const float* __
   }
   if (MODE == GH_POOL_MEAN) r = r / (float)n;
   if (MODE == GH_POOL_MAX && w == 0 && on) argmax[(size_t)cell * C + ch] = ra;
-  ghp_walk_store(order, lo, hi, [&](int p) { if (on) out[(size_t)p * os + ch] = r; });
+  ghr_walk_store(order, lo, hi, [&](int p) { if (on) out[(size_t)p * os + ch] = r; });
 }
 
 // ---- pool backward --------------------------------------------------------------------------------------------------------
@@ -207,19 +171,19 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_bwd_kernel(const float* __
   const bool on = ch < C;
   const int a = cell_start[cell], b = cell == n_cells ? T : cell_start[cell + 1], n = b - a;
   if (cell == n_cells) {
-    if (!ACC) ghp_walk_store(order, ghp_part(a, n, w), ghp_part(a, n, w + 1), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = 0.0f; });
+    if (!ACC) ghr_walk_store(order, ghr_part(a, n, w), ghr_part(a, n, w + 1), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = 0.0f; });
     return;
   }
   if (n <= 0) return;
-  const int lo = ghp_part(a, n, w), hi = ghp_part(a, n, w + 1);
+  const int lo = ghr_part(a, n, w), hi = ghr_part(a, n, w + 1);
   float acc = 0.0f;
-  ghp_walk(order, lo, hi, [&](int p) { return on ? g[(size_t)p * gs + ch] : 0.0f; }, [&](int, float v) { acc += v; });
+  ghr_walk(order, lo, hi, [&](int p) { return on ? g[(size_t)p * gs + ch] : 0.0f; }, [&](int, float v) { acc += v; });
   s_val[w][lane] = acc;
   __syncthreads();
   const float total = ((s_val[0][lane] + s_val[1][lane]) + s_val[2][lane]) + s_val[3][lane];
   if (MODE == GH_POOL_MEAN) {
     const float v = total / (float)n;
-    ghp_walk_store(order, lo, hi, [&](int p) {
+    ghr_walk_store(order, lo, hi, [&](int p) {
       if (on) { float* d = gx + (size_t)p * gxs + ch; *d = ACC ? *d + v : v; }
     });
   } else {
@@ -227,7 +191,7 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_pool_bwd_kernel(const float* __
     if (ACC) {
       if (w == 0 && am >= 0 && am < T) gx[(size_t)am * gxs + ch] += total;     // one (row, channel) per lane: nothing collides
     } else {
-      ghp_walk_store(order, lo, hi, [&](int p) { if (on) gx[(size_t)p * gxs + ch] = p == am ? total : 0.0f; });
+      ghr_walk_store(order, lo, hi, [&](int p) { if (on) gx[(size_t)p * gxs + ch] = p == am ? total : 0.0f; });
     }
   }
 }
@@ -244,11 +208,11 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_plane_fwd_kernel(const float* _
   if (threadIdx.x <= GHP_PLANE_CELLS) s_cs[threadIdx.x] = cell_start[min(c0 + (int)threadIdx.x, n_cells)];
   __syncthreads();
   const int A = s_cs[0], n = s_cs[GHP_PLANE_CELLS] - A;
-  const int lo = ghp_part(A, n, w), hi = ghp_part(A, n, w + 1);
+  const int lo = ghr_part(A, n, w), hi = ghr_part(A, n, w + 1);
   for (int cl = 0; cl < GHP_PLANE_CELLS; ++cl) {
     const int l = max(s_cs[cl], lo), h = min(s_cs[cl + 1], hi);
     float acc = 0.0f;
-    ghp_walk(order, l, h, [&](int p) { return on ? x[(size_t)p * xs + ch] : 0.0f; }, [&](int, float v) { acc += v; });
+    ghr_walk(order, l, h, [&](int p) { return on ? x[(size_t)p * xs + ch] : 0.0f; }, [&](int, float v) { acc += v; });
     s_part[w][cl][lane] = acc;
   }
   __syncthreads();
@@ -271,7 +235,7 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_plane_bwd_kernel(const float* _
   const bool on = ch < C;
   if (c0 >= n_cells) {                               // the workgroup after the last cells: points without a cell get zeros
     const int a = cell_start[n_cells], n = T - a;
-    ghp_walk_store(order, ghp_part(a, n, w), ghp_part(a, n, w + 1), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = 0.0f; });
+    ghr_walk_store(order, ghr_part(a, n, w), ghr_part(a, n, w + 1), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = 0.0f; });
     return;
   }
   if (threadIdx.x <= GHP_PLANE_CELLS) s_cs[threadIdx.x] = cell_start[min(c0 + (int)threadIdx.x, n_cells)];
@@ -287,10 +251,10 @@ __global__ __launch_bounds__(GHP_BLOCK) void ghp_plane_bwd_kernel(const float* _
   }
   __syncthreads();
   const int A = s_cs[0], n = s_cs[GHP_PLANE_CELLS] - A;
-  const int lo = ghp_part(A, n, w), hi = ghp_part(A, n, w + 1);
+  const int lo = ghr_part(A, n, w), hi = ghr_part(A, n, w + 1);
   for (int cl = 0; cl < GHP_PLANE_CELLS; ++cl) {
     const float v = s_t[cl][lane];
-    ghp_walk_store(order, max(s_cs[cl], lo), min(s_cs[cl + 1], hi), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = v; });
+    ghr_walk_store(order, max(s_cs[cl], lo), min(s_cs[cl + 1], hi), [&](int p) { if (on) gx[(size_t)p * gxs + ch] = v; });
   }
 }
 

@@ -9,6 +9,8 @@
 //   reduce    the per-workgroup partials of a backward are summed by a second launch, GHR_RED_EL elements x GHR_SEGMENTS runs per
 //             workgroup: a run is summed in workgroup order, then the runs in run order (ghr_reduce; head and vert).
 //   host      ghr_allow_lds (vert, cond): more than 64 KB of dynamic LDS, told to the runtime once per kernel.
+//   walk      pool and res: a wave walks a run of a plan's `order`, four rows in flight (ghr_walk, ghr_walk_store); ghr_part cuts a
+//             cell's list into the four waves' quarters.
 // gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage.
 #ifndef GH_ROWS_H
 #define GH_ROWS_H
@@ -186,6 +188,42 @@ __device__ __forceinline__ void ghr_linear_t(const float* gr, int m, const float
     if (k0 + 3 < ncols) emit(k0 + 3, a3);
   }
 }
+
+// ---- walking a run of a pooling plan's `order` (pool, res) ------------------------------------------------------------------------------
+// Calls f(point) for order[lo .. hi) in ascending position, 64 list entries fetched by one coalesced load and handed out by
+// v_readlane, four rows per step so that four loads are in flight. lo, hi are wave-uniform.
+template <typename Load, typename Use>
+__device__ __forceinline__ void ghr_walk(const int* __restrict__ order, int lo, int hi, Load load, Use use) {
+  const int lane = threadIdx.x & 63;
+  for (int j0 = lo; j0 < hi; j0 += 64) {
+    const int m = min(64, hi - j0);
+    const int mine = lane < m ? order[j0 + lane] : 0;
+    int k = 0;
+    for (; k + 4 <= m; k += 4) {
+      const int p0 = __builtin_amdgcn_readlane(mine, k), p1 = __builtin_amdgcn_readlane(mine, k + 1);
+      const int p2 = __builtin_amdgcn_readlane(mine, k + 2), p3 = __builtin_amdgcn_readlane(mine, k + 3);
+      const float v0 = load(p0), v1 = load(p1), v2 = load(p2), v3 = load(p3);
+      use(p0, v0); use(p1, v1); use(p2, v2); use(p3, v3);
+    }
+    for (; k < m; ++k) {
+      const int p = __builtin_amdgcn_readlane(mine, k);
+      use(p, load(p));
+    }
+  }
+}
+
+// the same walk for a pass that only writes
+template <typename Store>
+__device__ __forceinline__ void ghr_walk_store(const int* __restrict__ order, int lo, int hi, Store store) {
+  const int lane = threadIdx.x & 63;
+  for (int j0 = lo; j0 < hi; j0 += 64) {
+    const int m = min(64, hi - j0);
+    const int mine = lane < m ? order[j0 + lane] : 0;
+    for (int k = 0; k < m; ++k) store(__builtin_amdgcn_readlane(mine, k));
+  }
+}
+
+__device__ __forceinline__ int ghr_part(int a, int n, int w) { return a + (int)((long long)n * w / (GHR_BLOCK / 64)); }
 
 // A kernel that may ask for more than 64 KB of dynamic LDS says so, once per process, where the runtime wants to be told (the call sets
 // an upper limit, a CU's 160 KiB, and enqueues nothing). The flag belongs to the kernel, not to its function type: kernels of equal

@@ -358,14 +358,20 @@ def cell_index(p: torch.Tensor, radius: float, plane_size: int) -> torch.Tensor:
     return xi[..., 0] + plane_size * xi[..., 1]
 
 
-def pointnet_forward(self, p, ops: Optional[str] = None) -> torch.Tensor:
+def pointnet_forward(self, p, ops: Optional[str] = None, blocks: Optional[str] = None) -> torch.Tensor:
     """LocalPoolPointnet.forward(p) (pointnet_texture.py:89-114) over one PoolPlan per cloud: (B,T,D) -> (B, c_dim, plane, plane).
     Reads self.cfg.{radius, plane_size, scatter_type}, self.fc_pos, self.blocks, self.fc_c. ops="torch" runs the plain-torch
     restatement of the pooling on p's device instead of the kernels. A list in self.pool_record receives every pooled tensor.
     `p` may be a cond.PointRows standing for the (B,T,D) concatenation: the cell index then comes from its uv columns and the first
-    layer from PointRows.linear(self.fc_pos); the concatenation is not built."""
+    layer from PointRows.linear(self.fc_pos); the concatenation is not built.
+    blocks (or self.block_ops) = "folded" runs the ResNet blocks with the pooled half folded per cell and fc_c over the per-cell
+    means (res_block.folded_cloud): the (T,2H) cat buffers and the (T,c_dim) tensor are not built, and self.pool_record then
+    receives the pooled cell rows (n_cells, H) of every block instead of the (T,H) tensors. None or "torch": the statements below."""
     ops = ops or getattr(self, "pool_ops", "fused")
     check_ops(ops)
+    blocks = blocks or getattr(self, "block_ops", None) or "torch"
+    if blocks not in ("torch", "folded"):
+        raise ValueError(f"blocks must be None, 'torch' or 'folded', got {blocks!r}")
     given = isinstance(p, PointRows)
     if not given and p.dim() != 3:
         raise ValueError(f"p: expected (B, T, D), got {tuple(p.shape)}")
@@ -376,11 +382,16 @@ def pointnet_forward(self, p, ops: Optional[str] = None) -> torch.Tensor:
     if given:
         n_clouds = p.B
         index = cell_index(p.uv_columns(), float(cfg.radius), ps)
-        net = self.blocks[0](p.linear(self.fc_pos, ops))
+        first = p.linear(self.fc_pos, ops)
     else:
         n_clouds = p.shape[0]
         index = cell_index(p, float(cfg.radius), ps)
-        net = self.blocks[0](self.fc_pos(p))
+        first = self.fc_pos(p)
+    if blocks == "folded":
+        from .res_block import folded_cloud
+        fea = torch.stack([folded_cloud(self, first[b], PoolPlan(index[b], ps * ps), reduce, ops, record) for b in range(n_clouds)])
+        return fea.reshape(n_clouds, fea.shape[1], ps, ps)
+    net = self.blocks[0](first)
     planes = []
     for b in range(n_clouds):
         plan = PoolPlan(index[b], ps * ps)
@@ -402,11 +413,12 @@ def pointnet_forward(self, p, ops: Optional[str] = None) -> torch.Tensor:
 class LocalPoolPointnet(nn.Module):
     """The reference's point encoder (both `pointcloud_encoder_texture_cls` and `pointcloud_encoder_shade_cls` of every shipped
     config) with its state-dict keys — fc_pos, blocks.N.{fc_0, fc_1, shortcut}, fc_c — so a reference checkpoint loads unchanged.
-    Takes the reference's config mapping (`LocalPoolPointnet({"input_channels": 53, ...})`) or keywords."""
+    Takes the reference's config mapping (`LocalPoolPointnet({"input_channels": 53, ...})`) or keywords. blocks="folded" selects
+    the folded ResNet blocks (pointnet_forward)."""
 
     DEFAULTS = dict(input_channels=3, c_dim=128, hidden_dim=128, scatter_type="max", plane_size=32, n_blocks=5, radius=1.0)
 
-    def __init__(self, cfg=None, ops: str = "fused", **kw):
+    def __init__(self, cfg=None, ops: str = "fused", blocks: Optional[str] = None, **kw):
         super().__init__()
         given = dict(cfg or {})
         given.update(kw)
@@ -423,6 +435,7 @@ class LocalPoolPointnet(nn.Module):
         self.blocks = nn.ModuleList([ResnetBlockFC(2 * h, h) for _ in range(int(self.cfg.n_blocks))])
         self.fc_c = nn.Linear(h, int(self.cfg.c_dim))
         self.pool_ops = ops
+        self.block_ops = blocks          # None / "torch": the reference's statements; "folded": res_block (pointnet_forward)
         self.pool_record = None
 
     def forward(self, p: torch.Tensor) -> torch.Tensor:

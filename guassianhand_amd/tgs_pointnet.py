@@ -3,7 +3,10 @@
 
 The class is built on first access from the reference's own LocalPoolPointnet (pool.fused_pointnet_cls). That module imports
 `scatter_mean, scatter_max` from torch_scatter at its top; where no torch_scatter is installed, a module of that name holding
-pool.scatter_mean / pool.scatter_max is registered first, so the import succeeds without editing the reference."""
+pool.scatter_mean / pool.scatter_max is registered first, so the import succeeds without editing the reference.
+
+`LocalPoolPointnetFolded` is the same construction with block_ops = "folded": the ResNet blocks run with the pooled half folded per
+cell (guassianhand_amd.res_block)."""
 import importlib
 import sys
 import types
@@ -29,5 +32,11 @@ def __getattr__(name):
             from tgs.models.pointclouds.pointnet_texture import LocalPoolPointnet as base
             from .pool import fused_pointnet_cls
             _cache[name] = fused_pointnet_cls(base)
+        return _cache[name]
+    if name == "LocalPoolPointnetFolded":
+        if name not in _cache:
+            base = __getattr__("LocalPoolPointnet")
+            _cache[name] = type(name, (base,), {"block_ops": "folded", "__module__": __name__,
+                                                "__doc__": f"{base.__name__} with the ResNet blocks folded per cell"})
         return _cache[name]
     raise AttributeError(name)
