@@ -423,11 +423,47 @@ def declare_res(lib: C.CDLL) -> None:
 bind_res = declare_res          # for a caller that loads the library itself and binds this header alone
 
 
+# ---- include/gh_attn_rows.h: the row work around the attention core (a header of its own, as gh_res.h is) ----
+GH_ATTN_ROWS_MAX_H = 8
+GH_ATTN_ROWS_MAX_F = 192
+
+ATTN_ROWS_SYMBOLS = ("gh_attn_rows_workspace_bytes", "gh_attn_rows_pre_forward", "gh_attn_rows_post_forward", "gh_attn_rows_post_backward",
+                     "gh_attn_rows_pre_backward")
+ATTN_ROWS_PARAMS = ("wq_weight", "wq_bias", "wk_weight", "wk_bias", "wv_weight", "wv_bias", "ln1_weight", "ln1_bias", "fc_weight", "fc_bias",
+                    "ln2_weight", "ln2_bias", "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")
+
+
+class GhAttnRowsDims(C.Structure):
+    _fields_ = [("V", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("hid", C.c_int32), ("eps1", C.c_float), ("eps2", C.c_float),
+                ("x_stride", C.c_int64), ("out_stride", C.c_int64), ("dout_stride", C.c_int64), ("dx_stride", C.c_int64)]
+
+
+class GhAttnRowsParams(C.Structure):
+    """The module's sixteen tensors in state-dict order."""
+    _fields_ = [(n, C.c_void_p) for n in ATTN_ROWS_PARAMS]
+
+
+def declare_attn_rows(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_attn_rows.h declares."""
+    D, Pm, V = C.POINTER(GhAttnRowsDims), C.POINTER(GhAttnRowsParams), C.c_void_p
+    lib.gh_attn_rows_workspace_bytes.restype = C.c_size_t
+    lib.gh_attn_rows_workspace_bytes.argtypes = [D]
+    lib.gh_attn_rows_pre_forward.restype = C.c_int
+    lib.gh_attn_rows_pre_forward.argtypes = [D, Pm, V, V, V, V, V]
+    lib.gh_attn_rows_post_forward.restype = C.c_int
+    lib.gh_attn_rows_post_forward.argtypes = [D, Pm, V, V, V, V, V, V, V, V]
+    lib.gh_attn_rows_post_backward.restype = C.c_int
+    lib.gh_attn_rows_post_backward.argtypes = [D, Pm, V, V, V, V, V, V, V, C.c_size_t, V]
+    lib.gh_attn_rows_pre_backward.restype = C.c_int
+    lib.gh_attn_rows_pre_backward.argtypes = [D, Pm, V, V, V, V, V, V, V, C.c_size_t, V, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the ten headers (ALL_SYMBOLS)."""
-    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res):
+    """Attach argtypes/restypes for every symbol of the eleven headers (ALL_SYMBOLS)."""
+    for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
+                declare_attn_rows):
         one(lib)

@@ -11,7 +11,8 @@
 //   host      ghr_allow_lds (vert, cond): more than 64 KB of dynamic LDS, told to the runtime once per kernel.
 //   walk      pool and res: a wave walks a run of a plan's `order`, four rows in flight (ghr_walk, ghr_walk_store); ghr_part cuts a
 //             cell's list into the four waves' quarters.
-// gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage.
+// gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage. csrc_attn_rows/gh_attn_rows.hip takes the tile,
+// the layers and ghr_allow_lds, and gathers its rows through a list (ghr_stage_rows).
 #ifndef GH_ROWS_H
 #define GH_ROWS_H
 
@@ -50,6 +51,21 @@ __device__ __forceinline__ void ghr_stage(float* s, int pitch, const float* __re
       const int r = i / kc, c = i - r * kc;
       s[r * pitch + c] = r < nrows ? x[(row0 + r) * x_stride + k0 + c] : 0.f;
     }
+  }
+}
+
+// ghr_stage through a row list (attn_rows): tile row r is row idx[row0 + r] of x, or row row0 + r where idx is null; all kc columns
+// from column 0. Scalar loads: the start of a listed row has no alignment to count on.
+__device__ __forceinline__ void ghr_stage_rows(float* s, int pitch, const float* __restrict__ x, long long x_stride,
+                                               const int* __restrict__ idx, long long row0, int R, int nrows, int kc, int tid) {
+  for (int i = tid; i < R * kc; i += GHR_BLOCK) {
+    const int r = i / kc, c = i - r * kc;
+    float v = 0.f;
+    if (r < nrows) {
+      const long long src = idx ? (long long)idx[row0 + r] : row0 + r;
+      v = x[src * x_stride + c];
+    }
+    s[r * pitch + c] = v;
   }
 }
 

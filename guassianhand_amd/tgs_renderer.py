@@ -30,6 +30,13 @@ the HIP UV search (include/gh_uvd.h) instead of livehand's. `GS3DRendererFusedAl
 gate, refinement, head, fetch, attention and UV search. Opt-in too. The reference's modules import livehand at their top, which
 `uvd.install_livehand_shim()` serves where livehand is absent: resolving one of these four names calls it first.
 
+`GS3DRendererFusedAttnBlock` / `GS3DRendererEditFusedAttnBlock`: `GS3DRendererFusedAttn` whose `configure()` additionally calls
+`attn_block.fuse_attn_block(self)` — the whole `forward` of `self_attn_layer` (both LayerNorms, the projections, `fc`, the feed-forward
+block and the residuals, include/gh_attn_rows.h, around the attention core) is then three launches while its dropout is inactive and
+autograd asks none of its parameters for a gradient; otherwise it is what `GS3DRendererFusedAttn` does.
+`GS3DRendererFusedAllFetchAttnBlock` / `GS3DRendererEditFusedAllFetchAttnBlock` add the same to `...FusedAllFetchAttn`, and
+`GS3DRendererFusedAllFetchAttnBlockUvd` / `GS3DRendererEditFusedAllFetchAttnBlockUvd` the UV search to that. Opt-in too.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
@@ -43,6 +50,9 @@ _SUFFIXES = {"FusedHead": (False, True, False, False, "the fused Gaussian head")
              "FusedAttn": (False, False, False, True, "the HIP attention core"),
              "FusedAllFetchAttn": (True, True, True, True, "the fused gate and refinement, Gaussian head, plane fetch and HIP attention core")}
 _UVD = {"FusedUvd": "", "FusedAllFetchAttnUvd": "FusedAllFetchAttn"}          # suffix -> the suffix of the class the UV search is added to
+# suffix -> (the suffix of the class it is added to, whether it adds the UV search; otherwise the attention block's graft)
+_BLOCK = {"FusedAttnBlock": ("FusedAttn", False), "FusedAllFetchAttnBlock": ("FusedAllFetchAttn", False),
+          "FusedAllFetchAttnBlockUvd": ("FusedAllFetchAttnBlock", True)}
 
 
 def _build(name):
@@ -82,6 +92,24 @@ def _build(name):
                 fuse_get_uvd(self)
 
             return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and the HIP UV search"})
+    for suffix, (inner, uvd) in _BLOCK.items():
+        if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
+            if uvd:
+                from .uvd import install_livehand_shim
+                install_livehand_shim()
+            base = __getattr__(name[:-len(suffix)] + inner)
+
+            def configure(self, *args, **kwargs):
+                base.configure(self, *args, **kwargs)
+                if uvd:
+                    from .uvd import fuse_get_uvd
+                    fuse_get_uvd(self)
+                else:
+                    from .attn_block import fuse_attn_block
+                    fuse_attn_block(self)
+
+            doc = "the HIP UV search" if uvd else "the fused attention block around it"
+            return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
     raise AttributeError(name)
 
 
