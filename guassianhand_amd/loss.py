@@ -21,6 +21,12 @@ def _l1_kernel(image, target, guard=None):
     b = target.detach().float().contiguous()
     if a.shape != b.shape:
         raise ValueError("image and target must have the same shape")
+    # the kernel reads both as float4: a contiguous view into a larger buffer (img[1:]) may start off a 16-byte boundary, and
+    # .contiguous() hands such a view back as it is. Only then is it copied (a fresh allocation is aligned).
+    if a.data_ptr() % 16:
+        a = a.clone()
+    if b.data_ptr() % 16:
+        b = b.clone()
     n = a.numel()
     loss = torch.empty((), dtype=torch.float32, device=a.device)
     grad = torch.empty_like(a)
