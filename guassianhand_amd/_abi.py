@@ -458,12 +458,34 @@ def declare_attn_rows(lib: C.CDLL) -> None:
     lib.gh_attn_rows_pre_backward.argtypes = [D, Pm, V, V, V, V, V, V, V, C.c_size_t, V, V]
 
 
+# ---- include/gh_scene.h: the texture scene code (a header of its own, as gh_attn_rows.h is) ----
+GH_SCENE_PER_PLANE = 1
+GH_SCENE_MAX_CI = 1024
+GH_SCENE_MAX_CO = 128
+GH_SCENE_MAX_TILES = 2147483647
+
+SCENE_SYMBOLS = ("gh_scene_code_forward", "gh_scene_code_backward")
+
+
+class GhSceneDims(C.Structure):
+    _fields_ = [("B", C.c_int32), ("Ci", C.c_int32), ("Co", C.c_int32), ("Np", C.c_int32), ("S", C.c_int32), ("flags", C.c_uint32)]
+
+
+def declare_scene(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_scene.h declares."""
+    D, V, L = C.POINTER(GhSceneDims), C.c_void_p, C.c_int64
+    lib.gh_scene_code_forward.restype = C.c_int
+    lib.gh_scene_code_forward.argtypes = [D, V, L, L, V, L, L, V, V, V, L, L, V, V]
+    lib.gh_scene_code_backward.restype = C.c_int
+    lib.gh_scene_code_backward.argtypes = [D, V, V, V, V, L, L, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the eleven headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the twelve headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows):
+                declare_attn_rows, declare_scene):
         one(lib)
