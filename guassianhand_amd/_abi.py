@@ -480,12 +480,30 @@ def declare_scene(lib: C.CDLL) -> None:
     lib.gh_scene_code_backward.argtypes = [D, V, V, V, V, L, L, V]
 
 
+# ---- include/gh_trunk.h: forward_gs's trunk MLP and Gaussian head in one pass (a header of its own, as gh_scene.h is) ----
+GH_TRUNK_SILU = 0
+GH_TRUNK_RELU = 1
+GH_TRUNK_ROWS = 128
+GH_TRUNK_MAX_CIN = 192
+
+TRUNK_SYMBOLS = ("gh_trunk_forward", "gh_trunk_backward")
+
+
+def declare_trunk(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_trunk.h declares."""
+    D, V, L, I = C.POINTER(GhHeadDesc), C.c_void_p, C.c_int64, C.c_int
+    lib.gh_trunk_forward.restype = C.c_int
+    lib.gh_trunk_forward.argtypes = [V, L, I, I, I, I, V] + [V] * 8 + [D, I] + [V] * 6 + [V]
+    lib.gh_trunk_backward.restype = C.c_int
+    lib.gh_trunk_backward.argtypes = [V, V, L, I, I, I, I] + [V] * 6 + [D, I] + [V] * 5 + [V, L, V, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the twelve headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the thirteen headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows, declare_scene):
+                declare_attn_rows, declare_scene, declare_trunk):
         one(lib)

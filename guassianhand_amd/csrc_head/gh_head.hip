@@ -32,23 +32,6 @@ struct GhhOut {  // the contiguous arrays of one direction, and which of them ma
 };
 enum { GHH_V_XYZ = 1, GHH_V_SCALING = 2, GHH_V_ROTATION = 4, GHH_V_OPACITY = 8, GHH_V_SHS = 16, GHH_V_RAW = 32 };
 
-// n floats of a tile's contiguous run of an output: 16-byte stores where the run's base allows, the tail element by element
-template <class F>
-__device__ __forceinline__ void ghh_store_run(float* __restrict__ dst, int n, bool vec, int tid, F f) {
-  if (vec) {
-    for (int q = tid; 4 * q < n; q += GHH_BLOCK) {
-      const int e = 4 * q;
-      if (e + 4 <= n) {
-        *(float4*)(dst + e) = make_float4(f(e), f(e + 1), f(e + 2), f(e + 3));
-      } else {
-        for (int j = e; j < n; ++j) dst[j] = f(j);
-      }
-    }
-  } else {
-    for (int e = tid; e < n; e += GHH_BLOCK) dst[e] = f(e);
-  }
-}
-
 // ---- forward ---------------------------------------------------------------------------------------------------------
 template <int NG>  // groups of 16 outputs: ceil(O / 16)
 __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restrict__ x, long long x_stride, int P, int Cin,
@@ -119,7 +102,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
              clipped = flags & GH_HEAD_CLIP_SCALING;
   const float max_step = (float)(1.2 / 32);
   const float* pt = pts + row0 * 3;
-  ghh_store_run(out.xyz + row0 * 3, nrows * 3, out.vec & GHH_V_XYZ, tid, [&](int e) {
+  ghr_store_run(out.xyz + row0 * 3, nrows * 3, out.vec & GHH_V_XYZ, tid, [&](int e) {
     const float p = pt[e];
     if (!xyz_off) return p;
     const int r = e / 3;
@@ -127,7 +110,7 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
     if (restrict_off) v = (ghr_sigmoid(v) - 0.5f) * max_step;
     return v + p;
   });
-  ghh_store_run(out.scaling + row0 * 3, nrows * 3, out.vec & GHH_V_SCALING, tid, [&](int e) {
+  ghr_store_run(out.scaling + row0 * 3, nrows * 3, out.vec & GHH_V_SCALING, tid, [&](int e) {
     const int r = e / 3;
     float s = expf(s_raw[r * RP + 3 + (e - 3 * r)]);
     if (clipped) s = fminf(fmaxf(s, 0.f), clip);
@@ -144,14 +127,14 @@ __global__ __launch_bounds__(GHH_BLOCK) void ghh_fwd_kernel(const float* __restr
       dst[0] = a / den; dst[1] = bq / den; dst[2] = c / den; dst[3] = d / den;
     }
   }
-  ghh_store_run(out.opacity + row0, nrows, out.vec & GHH_V_OPACITY, tid, [&](int e) { return ghr_sigmoid(s_raw[e * RP + 10]); });
-  ghh_store_run(out.shs + row0 * width, nrows * width, out.vec & GHH_V_SHS, tid, [&](int e) {
+  ghr_store_run(out.opacity + row0, nrows, out.vec & GHH_V_OPACITY, tid, [&](int e) { return ghr_sigmoid(s_raw[e * RP + 10]); });
+  ghr_store_run(out.shs + row0 * width, nrows * width, out.vec & GHH_V_SHS, tid, [&](int e) {
     const int r = e / width;
     const float v = s_raw[r * RP + 11 + (e - r * width)];
     return use_rgb ? ghr_sigmoid(v) : v;
   });
   if (out.raw) {
-    ghh_store_run(out.raw + row0 * O, nrows * O, out.vec & GHH_V_RAW, tid, [&](int e) {
+    ghr_store_run(out.raw + row0 * O, nrows * O, out.vec & GHH_V_RAW, tid, [&](int e) {
       const int r = e / O;
       return s_raw[r * RP + (e - r * O)];
     });

@@ -9,8 +9,8 @@
 // stay in the accumulators and are the B operand of the next product register by register, so the sum over them runs in the order
 // the registers hold their rows (gh_res.h). 32 rows x 128 channels are four accumulators; the forward keeps two such sets (h, out).
 // Results leave in runs of four floats per lane (the registers r & 3 are four consecutive channels).
-// A slab costs two barriers: every thread first issues all its loads of the slab (gr_fetch) and of its lane's sixteen x or g operands,
-// waits for the waves that still read the previous slab, and writes its share to LDS (gr_put).
+// A slab costs two barriers: every thread first issues all its loads of the slab (ghr_fetch) and of its lane's sixteen x or g operands,
+// waits for the waves that still read the previous slab, and writes its share to LDS (ghr_put).
 //
 // Cell kernels: gh_pool.hip's walk (gh_rows.h) with one 4-wave workgroup per (cell, 64-channel slab), lanes are channels; the
 // quarters are combined through LDS in quarter order.
@@ -35,40 +35,6 @@ typedef float gr_acc __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ int gr_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 __device__ __forceinline__ float gr_relu(float v) { return v < 0.f ? 0.f : v; }  // a NaN passes
-
-// One matrix window on its way into LDS: element (r, c) of the window W[row0 + r][col0 + c] goes to s[r * pitch + c]. The window has
-// 4 Q columns and IT * GR_BLOCK / Q rows, a thread moves IT runs of four floats. vec: W is 16-byte aligned and stride and col0 are
-// multiples of 4. gr_fetch issues every load of the window before anything waits for one; gr_put writes what it brought.
-template <int IT, int Q>
-struct GrSlab {
-  float v[IT][4];
-};
-
-template <int IT, int Q>
-__device__ __forceinline__ void gr_fetch(GrSlab<IT, Q>& t, const float* __restrict__ W, long long stride, int row0, int col0, int vec, int tid) {
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int i = tid + it * GR_BLOCK, r = i / Q, c = 4 * (i % Q);
-    const float* src = W + (long long)(row0 + r) * stride + col0 + c;
-    if (vec) {
-      const float4 v = *(const float4*)src;
-      t.v[it][0] = v.x; t.v[it][1] = v.y; t.v[it][2] = v.z; t.v[it][3] = v.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t.v[it][j] = src[j];
-    }
-  }
-}
-
-template <int IT, int Q>
-__device__ __forceinline__ void gr_put(const GrSlab<IT, Q>& t, float* s, int pitch, int tid) {
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int i = tid + it * GR_BLOCK, r = i / Q, c = 4 * (i % Q);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[r * pitch + c + j] = t.v[it][j];
-  }
-}
 
 // y holds [channel][point on the lane] of NT tiles of 32 channels: the lane writes its point's row from column col0, four floats a time.
 template <int NT>
@@ -121,15 +87,15 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
   }
   const float* xp = a.x + (live ? p : 0) * a.x_stride;
   for (int k0 = 0; k0 < a.Cin; k0 += GR_SLAB) {
-    GrSlab<NT, GR_SLAB / 4> wa, wb;                            // H rows x 32 columns each
-    gr_fetch(wa, a.W0, a.w0_stride, 0, k0, a.vec_w0, tid);
-    gr_fetch(wb, a.Ws, a.ws_stride, 0, k0, a.vec_ws, tid);
+    GhrSlab<NT, GR_SLAB / 4> wa, wb;                            // H rows x 32 columns each
+    ghr_fetch(wa, a.W0, a.w0_stride, 0, k0, a.vec_w0, tid);
+    ghr_fetch(wb, a.Ws, a.ws_stride, 0, k0, a.vec_ws, tid);
     float xv[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) xv[s] = live ? xp[k0 + 2 * s + half] : 0.f;
     __syncthreads();                                           // the previous slab has been read by every wave
-    gr_put(wa, s_a, GR_PITCH, tid);
-    gr_put(wb, s_b, GR_PITCH, tid);
+    ghr_put(wa, s_a, GR_PITCH, tid);
+    ghr_put(wb, s_b, GR_PITCH, tid);
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -154,10 +120,10 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
   }
 #pragma unroll
   for (int jt = 0; jt < NT; ++jt) {
-    GrSlab<NT, GR_SLAB / 4> w1;
-    gr_fetch(w1, a.W1, H, 0, 32 * jt, a.vec_w1, tid);
+    GhrSlab<NT, GR_SLAB / 4> w1;
+    ghr_fetch(w1, a.W1, H, 0, 32 * jt, a.vec_w1, tid);
     __syncthreads();
-    gr_put(w1, s_a, GR_PITCH, tid);
+    ghr_put(w1, s_a, GR_PITCH, tid);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -184,13 +150,13 @@ __device__ __forceinline__ void gr_t_times_g(gr_acc (&d)[NT], float* s_w, const 
                                              const float* __restrict__ gp, bool live, int tid, int col, int half) {
   constexpr int H = 32 * NT;
   for (int c0 = 0; c0 < H; c0 += GR_SLAB) {
-    GrSlab<NT, H / 4> w;                                       // 32 rows x H columns
-    gr_fetch(w, W, stride, c0, k0, vec, tid);
+    GhrSlab<NT, H / 4> w;                                       // 32 rows x H columns
+    ghr_fetch(w, W, stride, c0, k0, vec, tid);
     float gv[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) gv[s] = live ? gp[c0 + 2 * s + half] : 0.f;
     __syncthreads();
-    gr_put(w, s_w, H, tid);
+    ghr_put(w, s_w, H, tid);
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -235,10 +201,10 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_backward_kernel(GrBwd a) {  //
     }
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
-      GrSlab<NT, H / 4> w;
-      gr_fetch(w, a.W0, a.w0_stride, 32 * jt, k0, a.vec_w0, tid);
+      GhrSlab<NT, H / 4> w;
+      ghr_fetch(w, a.W0, a.w0_stride, 32 * jt, k0, a.vec_w0, tid);
       __syncthreads();
-      gr_put(w, s_w, H, tid);
+      ghr_put(w, s_w, H, tid);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < 16; ++k) {

@@ -11,6 +11,9 @@
 //   host      ghr_allow_lds (vert, cond): more than 64 KB of dynamic LDS, told to the runtime once per kernel.
 //   walk      pool and res: a wave walks a run of a plan's `order`, four rows in flight (ghr_walk, ghr_walk_store); ghr_part cuts a
 //             cell's list into the four waves' quarters.
+//   slabs     res and trunk: a window of a weight matrix on its way into LDS, every load issued before the barrier (ghr_fetch,
+//             ghr_fetch_in for a window that reaches past the matrix, ghr_put). head and trunk: a tile's contiguous run of an output
+//             (ghr_store_run).
 // gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage. csrc_attn_rows/gh_attn_rows.hip takes the tile,
 // the layers and ghr_allow_lds, and gathers its rows through a list (ghr_stage_rows).
 #ifndef GH_ROWS_H
@@ -240,6 +243,76 @@ __device__ __forceinline__ void ghr_walk_store(const int* __restrict__ order, in
 }
 
 __device__ __forceinline__ int ghr_part(int a, int n, int w) { return a + (int)((long long)n * w / (GHR_BLOCK / 64)); }
+
+// ---- weight slabs of the matrix-instruction row kernels (res, trunk) ------------------------------------------------------------------
+// One matrix window on its way into LDS: element (r, c) of the window W[row0 + r][col0 + c] goes to s[r * pitch + c]. The window has
+// 4 Q columns and IT * GHR_BLOCK / Q rows, a thread moves IT runs of four floats. vec: W is 16-byte aligned and stride and col0 are
+// multiples of 4. ghr_fetch issues every load of the window before anything waits for one; ghr_put writes what it brought.
+template <int IT, int Q>
+struct GhrSlab {
+  float v[IT][4];
+};
+
+template <int IT, int Q>
+__device__ __forceinline__ void ghr_fetch(GhrSlab<IT, Q>& t, const float* __restrict__ W, long long stride, int row0, int col0, int vec, int tid) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int i = tid + it * GHR_BLOCK, r = i / Q, c = 4 * (i % Q);
+    const float* src = W + (long long)(row0 + r) * stride + col0 + c;
+    if (vec) {
+      const float4 v = *(const float4*)src;
+      t.v[it][0] = v.x; t.v[it][1] = v.y; t.v[it][2] = v.z; t.v[it][3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t.v[it][j] = src[j];
+    }
+  }
+}
+
+// ghr_fetch of a window that may reach past the matrix: W has nrows rows of ncols columns, and what lies outside arrives as zeros
+template <int IT, int Q>
+__device__ __forceinline__ void ghr_fetch_in(GhrSlab<IT, Q>& t, const float* __restrict__ W, long long stride, int row0, int col0, int nrows,
+                                             int ncols, int vec, int tid) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int i = tid + it * GHR_BLOCK, r = row0 + i / Q, c = col0 + 4 * (i % Q);
+    const float* src = W + (long long)r * stride + c;
+    if (vec && r < nrows && c + 4 <= ncols) {
+      const float4 v = *(const float4*)src;
+      t.v[it][0] = v.x; t.v[it][1] = v.y; t.v[it][2] = v.z; t.v[it][3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t.v[it][j] = (r < nrows && c + j < ncols) ? src[j] : 0.f;
+    }
+  }
+}
+
+template <int IT, int Q>
+__device__ __forceinline__ void ghr_put(const GhrSlab<IT, Q>& t, float* s, int pitch, int tid) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int i = tid + it * GHR_BLOCK, r = i / Q, c = 4 * (i % Q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[r * pitch + c + j] = t.v[it][j];
+  }
+}
+
+// n floats of a tile's contiguous run of an output (head, trunk): 16-byte stores where the run's base allows, the tail element by element
+template <class F>
+__device__ __forceinline__ void ghr_store_run(float* __restrict__ dst, int n, bool vec, int tid, F f) {
+  if (vec) {
+    for (int q = tid; 4 * q < n; q += GHR_BLOCK) {
+      const int e = 4 * q;
+      if (e + 4 <= n) {
+        *(float4*)(dst + e) = make_float4(f(e), f(e + 1), f(e + 2), f(e + 3));
+      } else {
+        for (int j = e; j < n; ++j) dst[j] = f(j);
+      }
+    }
+  } else {
+    for (int e = tid; e < n; e += GHR_BLOCK) dst[e] = f(e);
+  }
+}
 
 // A kernel that may ask for more than 64 KB of dynamic LDS says so, once per process, where the runtime wants to be told (the call sets
 // an upper limit, a CU's 160 KiB, and enqueues nothing). The flag belongs to the kernel, not to its function type: kernels of equal

@@ -37,6 +37,13 @@ autograd asks none of its parameters for a gradient; otherwise it is what `GS3DR
 `GS3DRendererFusedAllFetchAttnBlock` / `GS3DRendererEditFusedAllFetchAttnBlock` add the same to `...FusedAllFetchAttn`, and
 `GS3DRendererFusedAllFetchAttnBlockUvd` / `GS3DRendererEditFusedAllFetchAttnBlockUvd` the UV search to that. Opt-in too.
 
+`GS3DRendererFusedTrunk` / `GS3DRendererEditFusedTrunk`: `configure()` additionally calls `gs_head.fuse_gs_head(self)` and
+`gs_trunk.fuse_forward_gs(self)` — `forward_gs`, the trunk MLP `mlp_net` and the Gaussian head behind it, is then one HIP pass each way
+(include/gh_trunk.h) while the trunk has two hidden layers with SiLU or ReLU, the tensors are float32 on the device and autograd asks
+no parameter of `mlp_net` or `gs_net` for a gradient; otherwise it is `mlp_net` in torch and then the fused head.
+`GS3DRendererFusedAllFetchAttnBlockTrunk` / `GS3DRendererEditFusedAllFetchAttnBlockTrunk` and `...FusedAllFetchAttnBlockUvdTrunk` add
+the same to the classes of those names without `Trunk`. Opt-in too.
+
 The classes are built on first access from the reference's own classes (renderer.fused_renderer_cls / fused_renderer_cls_edit), so
 importing this module needs nothing of the reference."""
 _cache = {}
@@ -53,6 +60,8 @@ _UVD = {"FusedUvd": "", "FusedAllFetchAttnUvd": "FusedAllFetchAttn"}          # 
 # suffix -> (the suffix of the class it is added to, whether it adds the UV search; otherwise the attention block's graft)
 _BLOCK = {"FusedAttnBlock": ("FusedAttn", False), "FusedAllFetchAttnBlock": ("FusedAllFetchAttn", False),
           "FusedAllFetchAttnBlockUvd": ("FusedAllFetchAttnBlock", True)}
+# suffix -> the suffix of the class the fused trunk (with the fused head behind it) is added to
+_TRUNK = {"FusedTrunk": "", "FusedAllFetchAttnBlockTrunk": "FusedAllFetchAttnBlock", "FusedAllFetchAttnBlockUvdTrunk": "FusedAllFetchAttnBlockUvd"}
 
 
 def _build(name):
@@ -110,6 +119,18 @@ def _build(name):
 
             doc = "the HIP UV search" if uvd else "the fused attention block around it"
             return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and {doc}"})
+    for suffix, inner in _TRUNK.items():
+        if name.endswith(suffix) and name[:-len(suffix)] in _BASES:
+            base = __getattr__(name[:-len(suffix)] + inner)
+
+            def configure(self, *args, **kwargs):
+                base.configure(self, *args, **kwargs)
+                from .gs_head import fuse_gs_head
+                from .gs_trunk import fuse_forward_gs
+                fuse_gs_head(self)
+                fuse_forward_gs(self)
+
+            return type(base.__name__, (base,), {"configure": configure, "__module__": __name__, "__doc__": f"{base.__doc__}, and the fused trunk"})
     raise AttributeError(name)
 
 
