@@ -3,10 +3,10 @@
 //
 // One product shape serves every kernel: v_mfma_f32_32x32x2_f32, D[i][j] = fma chain over k of A[i][k] * B[k][j].
 //   operands   lane l gives A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]: one float each.
-//   result     lane l holds column j = l & 31; its register r holds row ga_row(r, l >> 5) = (r & 3) + 8 (r >> 2) + 4 (l >> 5).
+//   result     lane l holds column j = l & 31; its register r holds row ghr_acc_row(r, l >> 5) (gh_rows.h's "columns").
 // So a result X is the B operand of a product that sums over X's rows with no lane movement: step r of that product takes register r
-// and the A operand's k is row ga_row(r, l >> 5). The owner of a workgroup's rows (queries in the forward and the dq kernel, keys in
-// the dk/dv kernel) is therefore kept on the lane in every first product, and the swept rows come from LDS.
+// and the A operand's k is row ghr_acc_row(r, l >> 5). The owner of a workgroup's rows (queries in the forward and the dq kernel,
+// keys in the dk/dv kernel) is therefore kept on the lane in every first product, and the swept rows come from LDS.
 //   forward    S^T = K Q^T  (keys x queries), P^T = softmax part, O^T += V^T P^T
 //   dk, dv     S = Q K^T, dP = dO V^T (queries x keys), dV^T += dO^T P, dK^T += Q^T dS
 //   dq         S^T = K Q^T, dP^T = V dO^T (keys x queries), dQ^T += K^T dS^T
@@ -30,12 +30,8 @@ static_assert(GHR_BLOCK == 256 && GA_BLOCK_ROWS == (GHR_BLOCK / 64) * GA_ROWS, "
 static_assert(GA_D == 32, "one 32x32 tile holds a head");
 static_assert(2 * GA_STAGE * GA_PITCH >= 4 * GA_ROWS * GA_PITCH, "the stage doubles as the four waves' transpose tiles");
 
-typedef float ga_acc __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int ga_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-__device__ __forceinline__ ga_acc ga_zero() {
-  ga_acc z;
+__device__ __forceinline__ ghr_acc ga_zero() {
+  ghr_acc z;
 #pragma unroll
   for (int r = 0; r < 16; ++r) z[r] = 0.f;
   return z;
@@ -49,28 +45,28 @@ __device__ __forceinline__ void ga_load_own(float (&reg)[16], const float* __res
 }
 
 // X = T Own^T: rows of the LDS tile t (from local row r0) against the lane's own row. X[tile row][own row on the lane].
-__device__ __forceinline__ ga_acc ga_tile_times_own(const float* t, int r0, const float (&own)[16], int col, int half) {
-  ga_acc x = ga_zero();
+__device__ __forceinline__ ghr_acc ga_tile_times_own(const float* t, int r0, const float (&own)[16], int col, int half) {
+  ghr_acc x = ga_zero();
   const float* a = t + (r0 + col) * GA_PITCH + half;
 #pragma unroll
   for (int s = 0; s < 16; ++s) x = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s], own[s], x, 0, 0, 0);
   return x;
 }
 
-// Y += T^T X: X's rows (register r = tile row ga_row(r, half)) are summed against the tile's rows read along d. Y[d][own row on the lane].
-__device__ __forceinline__ ga_acc ga_tile_t_times(ga_acc y, const float* t, int r0, const float (&x)[16], int col, int half) {
+// Y += T^T X: X's rows (register r = tile row ghr_acc_row(r, half)) are summed against the tile's rows read along d. Y[d][own row on the lane].
+__device__ __forceinline__ ghr_acc ga_tile_t_times(ghr_acc y, const float* t, int r0, const float (&x)[16], int col, int half) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) y = __builtin_amdgcn_mfma_f32_32x32x2f32(t[(r0 + ga_row(r, half)) * GA_PITCH + col], x[r], y, 0, 0, 0);
+  for (int r = 0; r < 16; ++r) y = __builtin_amdgcn_mfma_f32_32x32x2f32(t[(r0 + ghr_acc_row(r, half)) * GA_PITCH + col], x[r], y, 0, 0, 0);
   return y;
 }
 
 // y holds [d][own row on the lane] of the wave's 32 rows from row0; dst is (.., V, H * 32) contiguous at this (batch, head). The tile
 // crosses the wave's LDS region so that each half-wave stores one row of 32 floats. Every thread of the workgroup calls this.
-__device__ __forceinline__ void ga_store_rows(float* region, const ga_acc& y, float* __restrict__ dst, long long dst_stride, long long row0,
+__device__ __forceinline__ void ga_store_rows(float* region, const ghr_acc& y, float* __restrict__ dst, long long dst_stride, long long row0,
                                               int V, int col, int half) {
   __syncthreads();                                             // the stage this region overlays has been read by every wave
 #pragma unroll
-  for (int r = 0; r < 16; ++r) region[col * GA_PITCH + ga_row(r, half)] = y[r];
+  for (int r = 0; r < 16; ++r) region[col * GA_PITCH + ghr_acc_row(r, half)] = y[r];
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < 16; ++it) {
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_forward_kernel(GhAttnTensor q, G
 
   float qr[16];
   ga_load_own(qr, qv.p, qv.stride, row, V, half);
-  ga_acc o = ga_zero();
+  ghr_acc o = ga_zero();
   float m = -INFINITY, l = 0.f;
 
   for (int kt = 0; kt < V; kt += GA_STAGE) {
@@ -119,12 +115,12 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_forward_kernel(GhAttnTensor q, G
     ga_stage(s_v, vv, kt, GA_STAGE, V, tid);
     __syncthreads();
     for (int sub = 0; sub < GA_STAGE && kt + sub < V; sub += GA_ROWS) {
-      const ga_acc st = ga_tile_times_own(s_k, sub, qr, col, half);
+      const ghr_acc st = ga_tile_times_own(s_k, sub, qr, col, half);
       float p[16];
       float mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        p[r] = kt + sub + ga_row(r, half) < V ? st[r] / norm : -INFINITY;
+        p[r] = kt + sub + ghr_acc_row(r, half) < V ? st[r] / norm : -INFINITY;
         mx = fmaxf(mx, p[r]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_backward_kv_kernel(GhAttnTensor 
   float kr[16], vr[16];
   ga_load_own(kr, kv.p, kv.stride, row, V, half);
   ga_load_own(vr, vv.p, vv.stride, row, V, half);
-  ga_acc dkt = ga_zero(), dvt = ga_zero();
+  ghr_acc dkt = ga_zero(), dvt = ga_zero();
 
   for (int qt = 0; qt < V; qt += GA_ROWS) {
     __syncthreads();
@@ -194,12 +190,12 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_backward_kv_kernel(GhAttnTensor 
       s_delta[tid] = in ? delta[(long long)bh * V + qt + tid] : 0.f;
     }
     __syncthreads();
-    const ga_acc s = ga_tile_times_own(s_q, 0, kr, col, half);   // [query][key on the lane]
-    const ga_acc dp = ga_tile_times_own(s_g, 0, vr, col, half);
+    const ghr_acc s = ga_tile_times_own(s_q, 0, kr, col, half);   // [query][key on the lane]
+    const ghr_acc dp = ga_tile_times_own(s_g, 0, vr, col, half);
     float p[16], ds[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = ga_row(r, half);
+      const int i = ghr_acc_row(r, half);
       p[r] = (qt + i < V && row < V) ? expf(s[r] / norm - s_lse[i]) : 0.f;
       ds[r] = (p[r] * (dp[r] - s_delta[i])) / norm;
     }
@@ -230,7 +226,7 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_backward_q_kernel(GhAttnTensor q
   ga_load_own(gr, gv.p, gv.stride, row, V, half);
   const float lse_q = row < V ? lse[(long long)bh * V + row] : 0.f;
   const float delta_q = row < V ? delta[(long long)bh * V + row] : 0.f;
-  ga_acc dqt = ga_zero();
+  ghr_acc dqt = ga_zero();
 
   for (int kt = 0; kt < V; kt += GA_STAGE) {
     __syncthreads();
@@ -238,12 +234,12 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_backward_q_kernel(GhAttnTensor q
     ga_stage(s_v, vv, kt, GA_STAGE, V, tid);
     __syncthreads();
     for (int sub = 0; sub < GA_STAGE && kt + sub < V; sub += GA_ROWS) {
-      const ga_acc st = ga_tile_times_own(s_k, sub, qr, col, half);   // [key][query on the lane]
-      const ga_acc dpt = ga_tile_times_own(s_v, sub, gr, col, half);
+      const ghr_acc st = ga_tile_times_own(s_k, sub, qr, col, half);   // [key][query on the lane]
+      const ghr_acc dpt = ga_tile_times_own(s_v, sub, gr, col, half);
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float p = kt + sub + ga_row(r, half) < V ? expf(st[r] / norm - lse_q) : 0.f;
+        const float p = kt + sub + ghr_acc_row(r, half) < V ? expf(st[r] / norm - lse_q) : 0.f;
         ds[r] = (p * (dpt[r] - delta_q)) / norm;
       }
       dqt = ga_tile_t_times(dqt, s_k, sub, ds, col, half);
@@ -253,8 +249,6 @@ __global__ __launch_bounds__(GHR_BLOCK) void ga_backward_q_kernel(GhAttnTensor q
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-static inline bool ga_al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
 // GH_OK with *empty set when there is nothing to launch.
 static int ga_check_dims(const GhAttnDims* d, bool* empty) {
   *empty = true;
@@ -267,7 +261,7 @@ static int ga_check_dims(const GhAttnDims* d, bool* empty) {
 }
 
 static int ga_check_tensor(const GhAttnTensor* t) {
-  if (!t || !t->p || !ga_al4(t->p)) return GH_ERR_INVALID_ARG;
+  if (!t || !t->p || !ghr_al4(t->p)) return GH_ERR_INVALID_ARG;
   return GH_OK;
 }
 
@@ -287,7 +281,7 @@ extern "C" int gh_attn_forward(const GhAttnDims* dims, const GhAttnTensor* q, co
   const int rc = ga_check_dims(dims, &empty);
   if (rc != GH_OK) return rc;
   if (empty) return GH_OK;
-  if (ga_check_tensor(q) || ga_check_tensor(k) || ga_check_tensor(v) || !out || !lse || !ga_al4(out) || !ga_al4(lse)) return GH_ERR_INVALID_ARG;
+  if (ga_check_tensor(q) || ga_check_tensor(k) || ga_check_tensor(v) || !out || !lse || !ghr_al4(out) || !ghr_al4(lse)) return GH_ERR_INVALID_ARG;
   const dim3 grid((unsigned)((dims->V + GA_BLOCK_ROWS - 1) / GA_BLOCK_ROWS), (unsigned)(dims->BS * dims->H));
   (void)hipGetLastError();
   hipLaunchKernelGGL(ga_forward_kernel, grid, dim3(GHR_BLOCK), 0, (hipStream_t)hip_stream, *q, *k, *v, ga_vec(k), ga_vec(v), out, lse,
@@ -303,7 +297,7 @@ extern "C" int gh_attn_backward(const GhAttnDims* dims, const GhAttnTensor* q, c
   if (rc != GH_OK) return rc;
   if (empty) return GH_OK;
   if (ga_check_tensor(q) || ga_check_tensor(k) || ga_check_tensor(v) || ga_check_tensor(dout)) return GH_ERR_INVALID_ARG;
-  if (!out || !lse || !ga_al4(out) || !ga_al4(lse) || !ga_al4(dq) || !ga_al4(dk) || !ga_al4(dv)) return GH_ERR_INVALID_ARG;
+  if (!out || !lse || !ghr_al4(out) || !ghr_al4(lse) || !ghr_al4(dq) || !ghr_al4(dk) || !ghr_al4(dv)) return GH_ERR_INVALID_ARG;
   if (!dq && !dk && !dv) return GH_OK;
   if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
   if (ws_bytes < gh_attn_workspace_bytes(dims)) return GH_ERR_WORKSPACE_SMALL;

@@ -123,8 +123,6 @@ struct GhlLayout {
   size_t total;
 };
 
-static inline bool ghl_aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 static bool ghl_layout(int N, int C, int Hp, int Wp, GhlLayout* L) {
   if (N < 0 || C < 1 || Hp < 1 || Wp < 1) return false;
   if ((long long)Hp * Wp > INT_MAX || N > INT_MAX / 4 || (C + 63) / 64 > 65535) return false;
@@ -158,7 +156,7 @@ extern "C" int gh_plane_sample_forward(const float* plane, const float* uv, floa
   if (!ghl_layout(N, C, Hp, Wp, &L)) return GH_ERR_UNSUPPORTED;
   if (N == 0) return GH_OK;
   if (!plane || !uv || !out || !workspace) return GH_ERR_INVALID_ARG;
-  if (!ghl_aligned4(plane) || !ghl_aligned4(uv) || !ghl_aligned4(out) || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (!ghr_al4(plane) || !ghr_al4(uv) || !ghr_al4(out) || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
   if (ws_bytes < L.copy) return GH_ERR_WORKSPACE_SMALL;
   const int HW = Hp * Wp;
   (void)hipGetLastError();
@@ -171,9 +169,9 @@ extern "C" int gh_plane_sample_forward(const float* plane, const float* uv, floa
 
 extern "C" int gh_plane_index(const float* uv, int N, int Hp, int Wp, int32_t* texel_start, int32_t* pairs, float* w, void* workspace,
                               size_t ws_bytes, void* hip_stream) {
-  if (N < 0 || Hp < 1 || Wp < 1 || !texel_start || !ghl_aligned4(texel_start)) return GH_ERR_INVALID_ARG;
+  if (N < 0 || Hp < 1 || Wp < 1 || !texel_start || !ghr_al4(texel_start)) return GH_ERR_INVALID_ARG;
   if (N > 0 && (!uv || !pairs || !w || !workspace)) return GH_ERR_INVALID_ARG;
-  if (!ghl_aligned4(uv) || !ghl_aligned4(pairs) || !ghl_aligned4(w) || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (!ghr_al4(uv) || !ghr_al4(pairs) || !ghr_al4(w) || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
   if ((long long)Hp * Wp > GH_POOL_MAX_CELLS) return GH_ERR_UNSUPPORTED;
   GhlLayout L;
   if (!ghl_layout(N, 1, Hp, Wp, &L)) return GH_ERR_UNSUPPORTED;
@@ -199,7 +197,7 @@ extern "C" int gh_plane_sample_backward(const float* grad_out, const int32_t* te
                                         float* grad_plane, int N, int C, int Hp, int Wp, void* hip_stream) {
   if (N < 0 || C < 1 || Hp < 1 || Wp < 1 || !texel_start || !grad_plane) return GH_ERR_INVALID_ARG;
   if (N > 0 && (!grad_out || !pairs || !w)) return GH_ERR_INVALID_ARG;
-  if (!ghl_aligned4(grad_out) || !ghl_aligned4(texel_start) || !ghl_aligned4(pairs) || !ghl_aligned4(w) || !ghl_aligned4(grad_plane))
+  if (!ghr_al4(grad_out) || !ghr_al4(texel_start) || !ghr_al4(pairs) || !ghr_al4(w) || !ghr_al4(grad_plane))
     return GH_ERR_INVALID_ARG;
   GhlLayout L;
   if (!ghl_layout(N, C, Hp, Wp, &L)) return GH_ERR_UNSUPPORTED;

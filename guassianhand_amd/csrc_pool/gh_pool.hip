@@ -273,8 +273,6 @@ static bool ghp_plan_layout(int T, int n_cells, GhpPlanLayout* L) {
   return true;
 }
 
-static inline bool ghp_aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 // Two (T x width) windows of float rows: apart, or interleaved columns of rows of one stride (the halves of a cat buffer).
 static bool ghp_windows_ok(const float* a, int as, int aw, const float* b, int bs, int bw, int T) {
   const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(T - 1) * as + aw) * sizeof(float);
@@ -287,7 +285,7 @@ static bool ghp_windows_ok(const float* a, int as, int aw, const float* b, int b
 }
 
 static bool ghp_common_ok(int T, int C, int n_cells, const void* cell_start, const void* order) {
-  return T >= 1 && C >= 1 && n_cells >= 1 && cell_start && order && ghp_aligned4(cell_start) && ghp_aligned4(order);
+  return T >= 1 && C >= 1 && n_cells >= 1 && cell_start && order && ghr_al4(cell_start) && ghr_al4(order);
 }
 
 extern "C" size_t gh_pool_plan_workspace(int T, int n_cells) {
@@ -298,7 +296,7 @@ extern "C" size_t gh_pool_plan_workspace(int T, int n_cells) {
 extern "C" int gh_pool_plan(const void* index, int index_is_int64, int T, int n_cells, int32_t* cell_start, int32_t* order,
                             uint32_t* flag, void* workspace, size_t ws_bytes, void* hip_stream) {
   if (T < 1 || n_cells < 1 || !index || !cell_start || !order || !flag || !workspace) return GH_ERR_INVALID_ARG;
-  if (!ghp_aligned4(cell_start) || !ghp_aligned4(order) || !ghp_aligned4(flag) || ((uintptr_t)workspace & 15) != 0 ||
+  if (!ghr_al4(cell_start) || !ghr_al4(order) || !ghr_al4(flag) || ((uintptr_t)workspace & 15) != 0 ||
       ((uintptr_t)index & (index_is_int64 ? 7 : 3)) != 0)
     return GH_ERR_INVALID_ARG;
   if (n_cells > GH_POOL_MAX_CELLS) return GH_ERR_UNSUPPORTED;
@@ -325,10 +323,10 @@ static inline dim3 ghp_cell_grid(int n_cells, int C) { return dim3((unsigned)(n_
 extern "C" int gh_pool_forward(const float* x, int x_stride, int T, int C, int n_cells, const int32_t* cell_start,
                                const int32_t* order, int reduce, float* out, int out_stride, int out_col, int32_t* argmax,
                                void* hip_stream) {
-  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !x || !out || !ghp_aligned4(x) || !ghp_aligned4(out))
+  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !x || !out || !ghr_al4(x) || !ghr_al4(out))
     return GH_ERR_INVALID_ARG;
   if (reduce != GH_POOL_MAX && reduce != GH_POOL_MEAN) return GH_ERR_INVALID_ARG;
-  if (reduce == GH_POOL_MAX && (!argmax || !ghp_aligned4(argmax))) return GH_ERR_INVALID_ARG;
+  if (reduce == GH_POOL_MAX && (!argmax || !ghr_al4(argmax))) return GH_ERR_INVALID_ARG;
   if (x_stride < C || out_col < 0 || (long long)out_stride < (long long)out_col + C) return GH_ERR_INVALID_ARG;
   if (!ghp_windows_ok(x, x_stride, C, out + out_col, out_stride, C, T)) return GH_ERR_INVALID_ARG;
   if (n_cells > GH_POOL_MAX_CELLS || (C + 63) / 64 > 65535) return GH_ERR_UNSUPPORTED;
@@ -347,10 +345,10 @@ extern "C" int gh_pool_forward(const float* x, int x_stride, int T, int C, int n
 extern "C" int gh_pool_backward(const float* grad_out, int g_stride, int g_col, int T, int C, int n_cells,
                                 const int32_t* cell_start, const int32_t* order, int reduce, const int32_t* argmax, float* grad_x,
                                 int gx_stride, int accumulate, void* hip_stream) {
-  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !grad_out || !grad_x || !ghp_aligned4(grad_out) || !ghp_aligned4(grad_x))
+  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !grad_out || !grad_x || !ghr_al4(grad_out) || !ghr_al4(grad_x))
     return GH_ERR_INVALID_ARG;
   if (reduce != GH_POOL_MAX && reduce != GH_POOL_MEAN) return GH_ERR_INVALID_ARG;
-  if (reduce == GH_POOL_MAX && (!argmax || !ghp_aligned4(argmax))) return GH_ERR_INVALID_ARG;
+  if (reduce == GH_POOL_MAX && (!argmax || !ghr_al4(argmax))) return GH_ERR_INVALID_ARG;
   if (gx_stride < C || g_col < 0 || (long long)g_stride < (long long)g_col + C) return GH_ERR_INVALID_ARG;
   if (!ghp_windows_ok(grad_x, gx_stride, C, grad_out + g_col, g_stride, C, T)) return GH_ERR_INVALID_ARG;
   if (n_cells > GH_POOL_MAX_CELLS || (C + 63) / 64 > 65535) return GH_ERR_UNSUPPORTED;
@@ -372,7 +370,7 @@ extern "C" int gh_pool_backward(const float* grad_out, int g_stride, int g_col, 
 
 extern "C" int gh_plane_mean_forward(const float* x, int x_stride, int T, int C, int n_cells, const int32_t* cell_start,
                                      const int32_t* order, float* plane, void* hip_stream) {
-  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !x || !plane || !ghp_aligned4(x) || !ghp_aligned4(plane))
+  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !x || !plane || !ghr_al4(x) || !ghr_al4(plane))
     return GH_ERR_INVALID_ARG;
   if (x_stride < C) return GH_ERR_INVALID_ARG;
   const uintptr_t p0 = (uintptr_t)plane, p1 = (uintptr_t)(plane + (size_t)C * n_cells);
@@ -388,7 +386,7 @@ extern "C" int gh_plane_mean_forward(const float* x, int x_stride, int T, int C,
 
 extern "C" int gh_plane_mean_backward(const float* grad_plane, int T, int C, int n_cells, const int32_t* cell_start,
                                       const int32_t* order, float* grad_x, int gx_stride, void* hip_stream) {
-  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !grad_plane || !grad_x || !ghp_aligned4(grad_plane) || !ghp_aligned4(grad_x))
+  if (!ghp_common_ok(T, C, n_cells, cell_start, order) || !grad_plane || !grad_x || !ghr_al4(grad_plane) || !ghr_al4(grad_x))
     return GH_ERR_INVALID_ARG;
   if (gx_stride < C) return GH_ERR_INVALID_ARG;
   const uintptr_t p0 = (uintptr_t)grad_plane, p1 = (uintptr_t)(grad_plane + (size_t)C * n_cells);

@@ -1,16 +1,13 @@
 // gh_res.hip — the point encoders' ResNet blocks with the pooled half folded per cell (include/gh_res.h).
 //
-// Row kernels. One product shape, v_mfma_f32_32x32x2_f32: D[i][j] = fma chain over k of A[i][k] * B[k][j], exact float32.
-//   operands   lane l gives A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]: one float each.
-//   result     lane l holds column j = l & 31; its register r holds row gr_row(r, l >> 5) = (r & 3) + 8 (r >> 2) + 4 (l >> 5).
-// The point is the column: a wave owns 32 rows of x, lane l the point l & 31, and every product is [channel][point]. The weights are
-// the A operand and come from LDS, where the four waves of a workgroup share one slab: 32 columns of all H rows in the forward (read
-// along the row, pitch 33), 32 rows of up to 128 columns in the backward (read along the column: the product is with W^T). h and dh
-// stay in the accumulators and are the B operand of the next product register by register, so the sum over them runs in the order
-// the registers hold their rows (gh_res.h). 32 rows x 128 channels are four accumulators; the forward keeps two such sets (h, out).
-// Results leave in runs of four floats per lane (the registers r & 3 are four consecutive channels).
-// A slab costs two barriers: every thread first issues all its loads of the slab (ghr_fetch) and of its lane's sixteen x or g operands,
-// waits for the waves that still read the previous slab, and writes its share to LDS (ghr_put).
+// Row kernels. One product shape, gh_rows.h's "columns": v_mfma_f32_32x32x2_f32, D[i][j] = fma chain over k of A[i][k] * B[k][j],
+// exact float32, with the point as the column: a wave owns 32 rows of x, lane l the point l & 31, and every product is
+// [channel][point]. The weights are the A operand and come from LDS, where the four waves of a workgroup share one slab: 32 columns
+// of all H rows in the forward (read along the row, pitch 33), 32 rows of up to 128 columns in the backward (read along the column:
+// the product is with W^T); every window lies inside its matrix (ghr_fetch, unchecked). h and dh stay in the accumulators and are the
+// B operand of the next product register by register, so the sum over them runs in the order the registers hold their rows
+// (gh_res.h). 32 rows x 128 channels are four accumulators; the forward keeps two such sets (h, out). The forward's first loop runs
+// two chains from one pass over x's slabs and is written out here; the other products are gh_rows.h's (ghr_mm, ghr_mm_t, ghr_mm_tg).
 //
 // Cell kernels: gh_pool.hip's walk (gh_rows.h) with one 4-wave workgroup per (cell, 64-channel slab), lanes are channels; the
 // quarters are combined through LDS in quarter order.
@@ -26,33 +23,11 @@
 #define GR_BLOCK GHR_BLOCK
 #define GR_WAVE_ROWS 32
 #define GR_SLAB 32   // columns (forward) or rows (backward) of a weight slab
-#define GR_PITCH 33  // the forward's slab: a lane reads along its own row
 
 static_assert(GH_RES_ROWS == (GR_BLOCK / 64) * GR_WAVE_ROWS, "four waves of 32 rows");
 static_assert(GH_RES_MAX_H == 4 * 32, "four accumulators of 32 channels");
 
-typedef float gr_acc __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int gr_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 __device__ __forceinline__ float gr_relu(float v) { return v < 0.f ? 0.f : v; }  // a NaN passes
-
-// y holds [channel][point on the lane] of NT tiles of 32 channels: the lane writes its point's row from column col0, four floats a time.
-template <int NT>
-__device__ __forceinline__ void gr_store(const gr_acc (&y)[NT], float* __restrict__ row, int col0, int half, bool live, int vec) {
-  if (!live) return;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float* d = row + col0 + 32 * t + 8 * q + 4 * half;
-      if (vec) {
-        *(float4*)d = make_float4(y[t][4 * q], y[t][4 * q + 1], y[t][4 * q + 2], y[t][4 * q + 3]);
-      } else {
-        d[0] = y[t][4 * q]; d[1] = y[t][4 * q + 1]; d[2] = y[t][4 * q + 2]; d[3] = y[t][4 * q + 3];
-      }
-    }
-  }
-}
 
 struct GrFwd {
   const float *x, *u, *s, *W0, *Ws, *W1;
@@ -66,9 +41,9 @@ struct GrFwd {
 template <int NT>
 __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
   constexpr int H = 32 * NT;
-  __shared__ float s_w[2 * H * GR_PITCH];
+  __shared__ float s_w[2 * H * GHR_WP];
   float* s_a = s_w;
-  float* s_b = s_w + H * GR_PITCH;
+  float* s_b = s_w + H * GHR_WP;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const long long p = (long long)blockIdx.x * GH_RES_ROWS + wave * GR_WAVE_ROWS + col;
   const bool live = p < a.T;
@@ -76,13 +51,13 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
   r = r < 0 ? 0 : (r >= a.R ? a.R - 1 : r);
   const float* ur = a.u + (long long)r * H;
   const float* sr = a.s + (long long)r * H;
-  gr_acc h[NT], o[NT];
+  ghr_acc h[NT], o[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      h[t][k] = ur[32 * t + gr_row(k, half)];
-      o[t][k] = sr[32 * t + gr_row(k, half)];
+      h[t][k] = ur[32 * t + ghr_acc_row(k, half)];
+      o[t][k] = sr[32 * t + ghr_acc_row(k, half)];
     }
   }
   const float* xp = a.x + (live ? p : 0) * a.x_stride;
@@ -94,15 +69,15 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
 #pragma unroll
     for (int s = 0; s < 16; ++s) xv[s] = live ? xp[k0 + 2 * s + half] : 0.f;
     __syncthreads();                                           // the previous slab has been read by every wave
-    ghr_put(wa, s_a, GR_PITCH, tid);
-    ghr_put(wb, s_b, GR_PITCH, tid);
+    ghr_put(wa, s_a, GHR_WP, tid);
+    ghr_put(wb, s_b, GHR_WP, tid);
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       const float xr = gr_relu(xv[s]);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const int w = (32 * t + col) * GR_PITCH + 2 * s + half;
+        const int w = (32 * t + col) * GHR_WP + 2 * s + half;
         h[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_a[w], xr, h[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_b[w], xv[s], o[t], 0, 0, 0);
       }
@@ -113,27 +88,13 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_forward_kernel(GrFwd a) {
     for (int t = 0; t < NT; ++t) {
       unsigned m = 0u;
 #pragma unroll
-      for (int k = 0; k < 16; ++k) m |= (h[t][k] > 0.f ? 1u : 0u) << gr_row(k, half);
+      for (int k = 0; k < 16; ++k) m |= (h[t][k] > 0.f ? 1u : 0u) << ghr_acc_row(k, half);
       m |= (unsigned)__shfl_xor((int)m, 32);
       if (half == 0 && live) a.mask[p * NT + t] = m;
     }
   }
-#pragma unroll
-  for (int jt = 0; jt < NT; ++jt) {
-    GhrSlab<NT, GR_SLAB / 4> w1;
-    ghr_fetch(w1, a.W1, H, 0, 32 * jt, a.vec_w1, tid);
-    __syncthreads();
-    ghr_put(w1, s_a, GR_PITCH, tid);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const float hv = gr_relu(h[jt][k]);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_a[(32 * t + col) * GR_PITCH + gr_row(k, half)], hv, o[t], 0, 0, 0);
-    }
-  }
-  gr_store<NT>(o, a.out + (live ? p : 0) * a.out_stride, 0, half, live, a.vec_out);
+  ghr_mm<true, NT, NT>(o, NT, h, [](float v) { return gr_relu(v); }, s_a, a.W1, H, a.vec_w1, tid, col, half);
+  ghr_store_tiles<NT>(o, a.out + (live ? p : 0) * a.out_stride, half, live, a.vec_out);
 }
 
 struct GrBwd {
@@ -143,28 +104,6 @@ struct GrBwd {
   long long g_stride, x_stride, w0_stride, ws_stride, dx_stride;
   int T, Cin, vec_w0, vec_ws, vec_w1, vec_dx, vec_dh;
 };
-
-// d[t] += (rows c0 .. c0 + 31 of W, columns k0 .. k0 + H)^T . g[p, c0 ..]: the slab's rows in ascending order
-template <int NT>
-__device__ __forceinline__ void gr_t_times_g(gr_acc (&d)[NT], float* s_w, const float* __restrict__ W, long long stride, int k0, int vec,
-                                             const float* __restrict__ gp, bool live, int tid, int col, int half) {
-  constexpr int H = 32 * NT;
-  for (int c0 = 0; c0 < H; c0 += GR_SLAB) {
-    GhrSlab<NT, H / 4> w;                                       // 32 rows x H columns
-    ghr_fetch(w, W, stride, c0, k0, vec, tid);
-    float gv[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) gv[s] = live ? gp[c0 + 2 * s + half] : 0.f;
-    __syncthreads();
-    ghr_put(w, s_w, H, tid);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[(2 * s + half) * H + 32 * t + col], gv[s], d[t], 0, 0, 0);
-    }
-  }
-}
 
 template <int NT>
 __global__ __launch_bounds__(GR_BLOCK, 2) void gr_backward_kernel(GrBwd a) {  // two waves per SIMD: 256 registers
@@ -177,52 +116,31 @@ __global__ __launch_bounds__(GR_BLOCK, 2) void gr_backward_kernel(GrBwd a) {  //
   const float* gp = a.g + pl * a.g_stride;
   const float* xp = a.x + pl * a.x_stride;
 
-  gr_acc dh[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) dh[t][k] = 0.f;
-  }
-  gr_t_times_g<NT>(dh, s_w, a.W1, H, 0, a.vec_w1, gp, live, tid, col, half);
+  ghr_acc dh[NT];
+  ghr_fill<NT>(dh, nullptr, half);
+  ghr_mm_tg<true, NT>(dh, s_w, a.W1, H, 0, H, H, a.vec_w1, gp, live, tid, col, half);
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const unsigned m = live ? a.mask[p * NT + t] : 0u;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) dh[t][k] = ((m >> gr_row(k, half)) & 1u) ? dh[t][k] : 0.f;
+    for (int k = 0; k < 16; ++k) dh[t][k] = ((m >> ghr_acc_row(k, half)) & 1u) ? dh[t][k] : 0.f;
   }
-  if (a.dh) gr_store<NT>(dh, a.dh + pl * H, 0, half, live, a.vec_dh);
+  if (a.dh) ghr_store_tiles<NT>(dh, a.dh + pl * H, half, live, a.vec_dh);
 
   for (int k0 = 0; k0 < a.Cin; k0 += H) {
-    gr_acc d[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) d[t][k] = 0.f;
-    }
-#pragma unroll
-    for (int jt = 0; jt < NT; ++jt) {
-      GhrSlab<NT, H / 4> w;
-      ghr_fetch(w, a.W0, a.w0_stride, 32 * jt, k0, a.vec_w0, tid);
-      __syncthreads();
-      ghr_put(w, s_w, H, tid);
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[gr_row(k, half) * H + 32 * t + col], dh[jt][k], d[t], 0, 0, 0);
-      }
-    }
+    ghr_acc d[NT];
+    ghr_fill<NT>(d, nullptr, half);
+    ghr_mm_t<true, NT, NT>(d, NT, dh, s_w, a.W0, a.w0_stride, k0, a.Cin, a.vec_w0, tid, col, half);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const float xv = live ? xp[k0 + 32 * t + gr_row(k, half)] : 0.f;
+        const float xv = live ? xp[k0 + 32 * t + ghr_acc_row(k, half)] : 0.f;
         d[t][k] = xv > 0.f ? d[t][k] : 0.f;
       }
     }
-    gr_t_times_g<NT>(d, s_w, a.Ws, a.ws_stride, k0, a.vec_ws, gp, live, tid, col, half);
-    gr_store<NT>(d, a.dx + pl * a.dx_stride, k0, half, live, a.vec_dx);
+    ghr_mm_tg<true, NT>(d, s_w, a.Ws, a.ws_stride, k0, H, a.Cin, a.vec_ws, gp, live, tid, col, half);
+    ghr_store_tiles<NT>(d, a.dx + pl * a.dx_stride + k0, half, live, a.vec_dx);
   }
 }
 
@@ -290,7 +208,6 @@ __global__ __launch_bounds__(GR_BLOCK) void gr_cell_max_bwd_kernel(const float* 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-static inline bool gr_al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 static inline int gr_vec(const void* p, long long stride) { return ghr_al16(p) && stride % 4 == 0; }
 
 static bool gr_dims_ok(int T, int Cin, int H) {
@@ -302,7 +219,8 @@ extern "C" int gh_res_forward(const float* x, int64_t x_stride, int T, int Cin, 
                               const float* W1, float* out, int64_t out_stride, uint32_t* mask, void* hip_stream) {
   if (!gr_dims_ok(T, Cin, H) || R < 1) return GH_ERR_INVALID_ARG;
   if (!x || !u || !s || !W0 || !Ws || !W1 || !out) return GH_ERR_INVALID_ARG;
-  if (!gr_al4(x) || !gr_al4(u) || !gr_al4(s) || !gr_al4(W0) || !gr_al4(Ws) || !gr_al4(W1) || !gr_al4(out) || !gr_al4(row_of) || !gr_al4(mask))
+  if (!ghr_al4(x) || !ghr_al4(u) || !ghr_al4(s) || !ghr_al4(W0) || !ghr_al4(Ws) || !ghr_al4(W1) || !ghr_al4(out) || !ghr_al4(row_of) ||
+      !ghr_al4(mask))
     return GH_ERR_INVALID_ARG;
   if (x_stride < Cin || w0_stride < Cin || ws_stride < Cin || out_stride < H) return GH_ERR_INVALID_ARG;
   if (T == 0) return GH_OK;
@@ -314,12 +232,7 @@ extern "C" int gh_res_forward(const float* x, int64_t x_stride, int T, int Cin, 
   const dim3 grid((unsigned)(((long long)T + GH_RES_ROWS - 1) / GH_RES_ROWS));
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();
-  switch (H / 32) {
-    case 1: hipLaunchKernelGGL(gr_forward_kernel<1>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(gr_forward_kernel<2>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(gr_forward_kernel<3>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    default: hipLaunchKernelGGL(gr_forward_kernel<4>, grid, dim3(GR_BLOCK), 0, st, a); break;
-  }
+  ghr_tiles(H / 32, [&](auto nt) { hipLaunchKernelGGL(gr_forward_kernel<nt()>, grid, dim3(GR_BLOCK), 0, st, a); });
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
 }
 
@@ -328,7 +241,7 @@ extern "C" int gh_res_backward(const float* g, int64_t g_stride, const float* x,
                                const float* W1, float* dx, int64_t dx_stride, float* dh, void* hip_stream) {
   if (!gr_dims_ok(T, Cin, H)) return GH_ERR_INVALID_ARG;
   if (!g || !x || !mask || !W0 || !Ws || !W1 || !dx) return GH_ERR_INVALID_ARG;
-  if (!gr_al4(g) || !gr_al4(x) || !gr_al4(mask) || !gr_al4(W0) || !gr_al4(Ws) || !gr_al4(W1) || !gr_al4(dx) || !gr_al4(dh))
+  if (!ghr_al4(g) || !ghr_al4(x) || !ghr_al4(mask) || !ghr_al4(W0) || !ghr_al4(Ws) || !ghr_al4(W1) || !ghr_al4(dx) || !ghr_al4(dh))
     return GH_ERR_INVALID_ARG;
   if (g_stride < H || x_stride < Cin || w0_stride < Cin || ws_stride < Cin || dx_stride < Cin) return GH_ERR_INVALID_ARG;
   if (T == 0) return GH_OK;
@@ -341,17 +254,12 @@ extern "C" int gh_res_backward(const float* g, int64_t g_stride, const float* x,
   const dim3 grid((unsigned)(((long long)T + GH_RES_ROWS - 1) / GH_RES_ROWS));
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();
-  switch (H / 32) {
-    case 1: hipLaunchKernelGGL(gr_backward_kernel<1>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(gr_backward_kernel<2>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(gr_backward_kernel<3>, grid, dim3(GR_BLOCK), 0, st, a); break;
-    default: hipLaunchKernelGGL(gr_backward_kernel<4>, grid, dim3(GR_BLOCK), 0, st, a); break;
-  }
+  ghr_tiles(H / 32, [&](auto nt) { hipLaunchKernelGGL(gr_backward_kernel<nt()>, grid, dim3(GR_BLOCK), 0, st, a); });
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
 }
 
 static int gr_cells_ok(int T, int C, int n_cells, const void* cell_start, const void* order) {
-  if (T < 0 || C < 1 || n_cells < 1 || !cell_start || !order || !gr_al4(cell_start) || !gr_al4(order)) return GH_ERR_INVALID_ARG;
+  if (T < 0 || C < 1 || n_cells < 1 || !cell_start || !order || !ghr_al4(cell_start) || !ghr_al4(order)) return GH_ERR_INVALID_ARG;
   if (n_cells > GH_POOL_MAX_CELLS || (C + 63) / 64 > 65535) return GH_ERR_UNSUPPORTED;
   return GH_OK;
 }
@@ -360,7 +268,7 @@ extern "C" int gh_res_cell_sum(const float* x, int64_t x_stride, int T, int C, i
                                const int32_t* order, int tail, float* y, void* hip_stream) {
   const int rc = gr_cells_ok(T, C, n_cells, cell_start, order);
   if (rc != GH_OK) return rc;
-  if (!x || !y || !gr_al4(x) || !gr_al4(y) || x_stride < C) return GH_ERR_INVALID_ARG;
+  if (!x || !y || !ghr_al4(x) || !ghr_al4(y) || x_stride < C) return GH_ERR_INVALID_ARG;
   if (T == 0) return GH_OK;
   (void)hipGetLastError();
   const dim3 grid((unsigned)(n_cells + (tail ? 1 : 0)), (unsigned)((C + 63) / 64));
@@ -373,7 +281,7 @@ extern "C" int gh_res_cell_max(const float* x, int64_t x_stride, int T, int C, i
                                const int32_t* order, float* vals, int32_t* argmax, void* hip_stream) {
   const int rc = gr_cells_ok(T, C, n_cells, cell_start, order);
   if (rc != GH_OK) return rc;
-  if (!x || !vals || !argmax || !gr_al4(x) || !gr_al4(vals) || !gr_al4(argmax) || x_stride < C) return GH_ERR_INVALID_ARG;
+  if (!x || !vals || !argmax || !ghr_al4(x) || !ghr_al4(vals) || !ghr_al4(argmax) || x_stride < C) return GH_ERR_INVALID_ARG;
   if (T == 0) return GH_OK;
   (void)hipGetLastError();
   const dim3 grid((unsigned)n_cells, (unsigned)((C + 63) / 64));
@@ -384,7 +292,7 @@ extern "C" int gh_res_cell_max(const float* x, int64_t x_stride, int T, int C, i
 
 extern "C" int gh_res_cell_max_backward(const float* gm, const int32_t* argmax, int T, int C, int n_cells, float* grad_x,
                                         int64_t gx_stride, void* hip_stream) {
-  if (T < 0 || C < 1 || n_cells < 1 || !gm || !argmax || !grad_x || !gr_al4(gm) || !gr_al4(argmax) || !gr_al4(grad_x) || gx_stride < C)
+  if (T < 0 || C < 1 || n_cells < 1 || !gm || !argmax || !grad_x || !ghr_al4(gm) || !ghr_al4(argmax) || !ghr_al4(grad_x) || gx_stride < C)
     return GH_ERR_INVALID_ARG;
   if (T == 0) return GH_OK;
   const long long total = (long long)n_cells * C;

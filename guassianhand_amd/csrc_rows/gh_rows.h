@@ -14,14 +14,22 @@
 //   slabs     res and trunk: a window of a weight matrix on its way into LDS, every load issued before the barrier (ghr_fetch,
 //             ghr_fetch_in for a window that reaches past the matrix, ghr_put). head and trunk: a tile's contiguous run of an output
 //             (ghr_store_run).
+//   columns   res, trunk, scene and attn: the 32x32x2 float32 matrix-instruction product with the point as the column — the accumulator
+//             and its register-to-row map (ghr_acc, ghr_acc_row). res and trunk: a set of accumulators filled with a bias or zeros
+//             (ghr_fill), and the products of a weight matrix that crosses LDS in slabs with an operand from memory (ghr_mm_x,
+//             ghr_mm_tg) or from the previous product's accumulators (ghr_mm, ghr_mm_t), the window whole or bounded at compile
+//             time. res: whole tiles stored to the lane's row (ghr_store_tiles). ghr_tiles is the host's switch into a kernel
+//             template's tile count.
 // gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage. csrc_attn_rows/gh_attn_rows.hip takes the tile,
-// the layers and ghr_allow_lds, and gathers its rows through a list (ghr_stage_rows).
+// the layers and ghr_allow_lds, and gathers its rows through a list (ghr_stage_rows). ghr_al4 is every block's test of a float pointer.
 #ifndef GH_ROWS_H
 #define GH_ROWS_H
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #define GHR_BLOCK 256
 #define GHR_ROWS 64      // rows per tile: lane = row
@@ -33,6 +41,7 @@ static_assert(GHR_BLOCK == 4 * GHR_ROWS, "lane = row, four waves share a row's c
 
 static inline size_t ghr_align(size_t x) { return (x + 255) & ~(size_t)255; }  // workspace parts start on 256 bytes
 static inline bool ghr_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static inline bool ghr_al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }  // a float array (null passes)
 
 __device__ __forceinline__ float ghr_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
@@ -311,6 +320,163 @@ __device__ __forceinline__ void ghr_store_run(float* __restrict__ dst, int n, bo
     }
   } else {
     for (int e = tid; e < n; e += GHR_BLOCK) dst[e] = f(e);
+  }
+}
+
+// ---- columns: the 32x32x2 float32 matrix-instruction product with the point as the column (res, trunk; scene and attn: the map) -------
+// v_mfma_f32_32x32x2_f32, D[i][j] = fma chain over k of A[i][k] * B[k][j]: lane l gives A[i = l & 31][k = l >> 5] and
+// B[k = l >> 5][j = l & 31], one float each, and holds column col = l & 31 of D; with half = l >> 5 its register r is row
+// ghr_acc_row(r, half). A wave owns 32 points, lane l the point col; tiles of 32 channels are accumulators.
+typedef float ghr_acc __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ int ghr_acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+template <int NT>
+__device__ __forceinline__ void ghr_fill(ghr_acc (&h)[NT], const float* __restrict__ b, int half) {  // b: the bias, or null for zeros
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) h[t][k] = b ? b[32 * t + ghr_acc_row(k, half)] : 0.f;
+  }
+}
+
+// y holds [channel][point on the lane] of NT tiles of 32 channels: the lane writes them to its point's row, four floats a time (the
+// registers r & 3 are four consecutive channels). For rows of whole tiles: a store with a column bound (the trunk's grad_x) stays with
+// its kernel, because here the compiler folds the bounded tail's fourth store into the 16-byte one and splits that into 12 + 4 bytes.
+template <int NT>
+__device__ __forceinline__ void ghr_store_tiles(const ghr_acc (&y)[NT], float* __restrict__ row, int half, bool live, int vec) {
+  if (!live) return;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float* d = row + 32 * t + 8 * q + 4 * half;
+      if (vec) {
+        *(float4*)d = make_float4(y[t][4 * q], y[t][4 * q + 1], y[t][4 * q + 2], y[t][4 * q + 3]);
+      } else {
+        d[0] = y[t][4 * q]; d[1] = y[t][4 * q + 1]; d[2] = y[t][4 * q + 2]; d[3] = y[t][4 * q + 3];
+      }
+    }
+  }
+}
+
+// The weights are the A operand and cross LDS in slabs the four waves share, two barriers a slab: every load of the slab and of the
+// lane's operands is issued, then the barrier behind the previous slab's readers, ghr_put, the barrier. A slab is 32 columns of a
+// matrix's rows, read along the row at pitch GHR_WP (W . src), or 32 rows of up to 128 columns, read along the column (W^T . src).
+// WHOLE: the window lies inside the matrix (ghr_fetch); otherwise what lies outside is zeros (ghr_fetch_in).
+#define GHR_WP 33
+
+template <bool WHOLE, int IT, int Q>
+__device__ __forceinline__ void ghr_window(GhrSlab<IT, Q>& t, const float* __restrict__ W, long long stride, int row0, int col0, int nrows,
+                                           int ncols, int vec, int tid) {
+  if constexpr (WHOLE) ghr_fetch(t, W, stride, row0, col0, vec, tid);
+  else ghr_fetch_in(t, W, stride, row0, col0, nrows, ncols, vec, tid);
+}
+
+// h[t] += W[32 t .., 0 .. n) . x: W (32 NH, n) contiguous, x = xp[0 .. n) (zeros where not live), k ascending; the last slab's
+// missing columns are zeros on both sides
+template <int NH>
+__device__ __forceinline__ void ghr_mm_x(ghr_acc (&h)[NH], float* s_w, const float* __restrict__ W, int n, int vec, const float* __restrict__ xp,
+                                         bool live, int tid, int col, int half) {
+  for (int k0 = 0; k0 < n; k0 += 32) {
+    const int kc = n - k0 < 32 ? n - k0 : 32;
+    GhrSlab<NH, 8> w;                                          // 32 NH rows x 32 columns
+    ghr_fetch_in(w, W, n, 0, k0, 32 * NH, n, vec, tid);
+    float xv[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) xv[s] = (live && 2 * s + half < kc) ? xp[k0 + 2 * s + half] : 0.f;
+    __syncthreads();                                           // the previous slab has been read by every wave
+    ghr_put(w, s_w, GHR_WP, tid);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      if (2 * s < kc) {
+#pragma unroll
+        for (int t = 0; t < NH; ++t)
+          h[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[(32 * t + col) * GHR_WP + 2 * s + half], xv[s], h[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// d[t] += W[32 t .., :] . f(src) for t < nt: W (nrows, 32 NS) contiguous, src's channels in register order, f the activation on the way
+template <bool WHOLE, int NS, int ND, class F>
+__device__ __forceinline__ void ghr_mm(ghr_acc (&d)[ND], int nt, const ghr_acc (&src)[NS], F f, float* s_w, const float* __restrict__ W,
+                                       int nrows, int vec, int tid, int col, int half) {
+#pragma unroll
+  for (int jt = 0; jt < NS; ++jt) {
+    GhrSlab<ND, 8> w;                                          // 32 ND rows x 32 columns
+    ghr_window<WHOLE>(w, W, 32 * NS, 0, 32 * jt, nrows, 32 * NS, vec, tid);
+    __syncthreads();
+    ghr_put(w, s_w, GHR_WP, tid);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const float hv = f(src[jt][k]);
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+        if (t < nt) d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[(32 * t + col) * GHR_WP + ghr_acc_row(k, half)], hv, d[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// d[t] += (W[:, c0 + 32 t ..])^T . src for t < nt: W (32 NS, ncols) with row stride `stride`, its rows in register order; the window is
+// 32 ND columns from c0
+template <bool WHOLE, int NS, int ND>
+__device__ __forceinline__ void ghr_mm_t(ghr_acc (&d)[ND], int nt, const ghr_acc (&src)[NS], float* s_w, const float* __restrict__ W,
+                                         long long stride, int c0, int ncols, int vec, int tid, int col, int half) {
+  constexpr int CW = 32 * ND;
+#pragma unroll
+  for (int jt = 0; jt < NS; ++jt) {
+    GhrSlab<ND, CW / 4> w;                                     // 32 rows x 32 ND columns
+    ghr_window<WHOLE>(w, W, stride, 32 * jt, c0, 32 * NS, ncols, vec, tid);
+    __syncthreads();
+    ghr_put(w, s_w, CW, tid);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+        if (t < nt) d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[ghr_acc_row(k, half) * CW + 32 * t + col], src[jt][k], d[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// d[t] += (W[0 .. n, c0 + 32 t ..])^T . g: g = gp[0 .. n) from memory or LDS (zeros where not live), the rows of W ascending; the
+// window is 32 ND columns from c0 of W's ncols. WHOLE: n is a multiple of 32 as well.
+template <bool WHOLE, int ND>
+__device__ __forceinline__ void ghr_mm_tg(ghr_acc (&d)[ND], float* s_w, const float* __restrict__ W, long long stride, int c0, int n, int ncols,
+                                          int vec, const float* __restrict__ gp, bool live, int tid, int col, int half) {
+  constexpr int CW = 32 * ND;
+  for (int r0 = 0; r0 < n; r0 += 32) {
+    GhrSlab<ND, CW / 4> w;                                     // 32 rows x 32 ND columns
+    ghr_window<WHOLE>(w, W, stride, r0, c0, n, ncols, vec, tid);
+    float gv[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) gv[s] = (live && (WHOLE || r0 + 2 * s + half < n)) ? gp[r0 + 2 * s + half] : 0.f;
+    __syncthreads();
+    ghr_put(w, s_w, CW, tid);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      if (WHOLE || r0 + 2 * s < n) {
+#pragma unroll
+        for (int t = 0; t < ND; ++t) d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_w[(2 * s + half) * CW + 32 * t + col], gv[s], d[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// f(std::integral_constant<int, n>) for a tile count n = 1 .. 4 (anything else is 4): a host switch into a kernel template
+template <class F>
+static inline void ghr_tiles(int n, F f) {
+  switch (n) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
   }
 }
 

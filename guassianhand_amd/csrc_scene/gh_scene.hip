@@ -3,7 +3,7 @@
 //
 // One product shape, v_mfma_f32_32x32x2_f32: D[i][n] = fma chain over k of A[i][k] * B[k][n], exact float32.
 //   operands   lane l gives A[i = l & 31][k = l >> 5] and B[k = l >> 5][n = l & 31]: one float each.
-//   result     lane l holds column n = l & 31; its register r holds row gs_row(r, l >> 5) = (r & 3) + 8 (r >> 2) + 4 (l >> 5).
+//   result     lane l holds column n = l & 31; its register r holds row ghr_acc_row(r, l >> 5) (gh_rows.h's "columns").
 // The token is the column everywhere: a wave owns 32 consecutive tokens of one batch element, lane l the token l & 31.
 //
 // Forward, D[j][t] = sum_c W[c][j] x[c][t]. The weight is (Ci, 4 Co) and the tokens are (Ci, T) per batch element: lane l reads
@@ -26,16 +26,13 @@
 #include <stdint.h>
 
 #include "../../include/gh_scene.h"
+#include "../csrc_rows/gh_rows.h"
 
 #define GS_WAVE 64
 #define GS_TILE 32
 #define GS_PITCH 33
 #define GS_FWD_STEPS 16  // chain steps (of two channels) whose operands are fetched at once
 #define GS_PB_BLOCK 256
-
-typedef float gs_acc __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int gs_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 struct GsFwd {
   const float *a, *b, *W, *cb, *pb;
@@ -71,7 +68,7 @@ __global__ __launch_bounds__(GS_WAVE) void gs_forward_kernel(GsFwd a) {
   const float* xa = a.a + b * a.a_sb + (live_t ? t : a.T - 1);
   const float* xb = HAS_B ? a.b + b * a.b_sb + (live_t ? t : a.T - 1) : xa;
 
-  gs_acc acc;
+  ghr_acc acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(GS_WAVE) void gs_backward_kernel(GsBwd a) {
   // the lane's texel (dy = 0, dx = half) of output channel 0
   const float* gp = a.g + ((a.per_plane ? (b * a.Np + p) * a.Co : b * a.Co) * S2 + 2 * y) * row_len + (a.per_plane ? 0 : p * S2) + 2 * x_ + half;
 
-  gs_acc acc;
+  ghr_acc acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
@@ -239,7 +236,7 @@ __global__ __launch_bounds__(GS_WAVE) void gs_backward_kernel(GsBwd a) {
   float* d = a.d_tok + b * a.Ci * a.T + t;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int c = c0 + gs_row(r, half);
+    const int c = c0 + ghr_acc_row(r, half);
     if (c < a.Ci) d[c * a.T] = acc[r];
   }
 }
@@ -260,8 +257,6 @@ __global__ __launch_bounds__(GS_PB_BLOCK) void gs_plane_bias_kernel(const float*
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-static inline bool gs_al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
 typedef unsigned __int128 gs_u128;
 
 // GH_OK with T and the tile counts of both products filled in, or the status the header names
@@ -291,7 +286,7 @@ extern "C" int gh_scene_code_forward(const GhSceneDims* dims, const float* tok_a
   const int rc = gs_dims(dims, &T, &tok_tiles, &j_tiles, &c_tiles);
   if (rc != GH_OK) return rc;
   if (!tok_a || !weight || !out) return GH_ERR_INVALID_ARG;
-  if (!gs_al4(tok_a) || !gs_al4(tok_b) || !gs_al4(weight) || !gs_al4(conv_bias) || !gs_al4(plane_bias) || !gs_al4(out)) return GH_ERR_INVALID_ARG;
+  if (!ghr_al4(tok_a) || !ghr_al4(tok_b) || !ghr_al4(weight) || !ghr_al4(conv_bias) || !ghr_al4(plane_bias) || !ghr_al4(out)) return GH_ERR_INVALID_ARG;
   if (a_stride_b < 0 || a_stride_c < 0 || (tok_b && (b_stride_b < 0 || b_stride_c < 0))) return GH_ERR_INVALID_ARG;
   const int per_plane = (dims->flags & GH_SCENE_PER_PLANE) ? 1 : 0;
   if (plane_bias && (per_plane || pb_stride_c < 0 || pb_stride_r < 0)) return GH_ERR_INVALID_ARG;
@@ -317,7 +312,7 @@ extern "C" int gh_scene_code_backward(const GhSceneDims* dims, const float* weig
   const int rc = gs_dims(dims, &T, &tok_tiles, &j_tiles, &c_tiles);
   if (rc != GH_OK) return rc;
   if (!weight || !dout) return GH_ERR_INVALID_ARG;
-  if (!gs_al4(weight) || !gs_al4(dout) || !gs_al4(d_tok) || !gs_al4(d_plane_bias)) return GH_ERR_INVALID_ARG;
+  if (!ghr_al4(weight) || !ghr_al4(dout) || !ghr_al4(d_tok) || !ghr_al4(d_plane_bias)) return GH_ERR_INVALID_ARG;
   const int per_plane = (dims->flags & GH_SCENE_PER_PLANE) ? 1 : 0;
   if (d_plane_bias && (per_plane || dpb_stride_c < 0 || dpb_stride_r < 0)) return GH_ERR_INVALID_ARG;
   if (dims->B == 0 || (!d_tok && !d_plane_bias)) return GH_OK;

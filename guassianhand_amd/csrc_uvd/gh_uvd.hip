@@ -195,8 +195,6 @@ struct GhuLayout {
   int split;
 };
 
-static inline bool ghu_aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 extern "C" int gh_uvd_auto_split(int N, int F) {
   if (N < 1 || F < 1) return 1;
   const int blocks = (int)(((long long)N + GHU_BLOCK - 1) / GHU_BLOCK);
@@ -229,8 +227,8 @@ extern "C" int gh_uvd_forward(const float* points, int N, const float* verts, in
   if (V < 1 || !ghu_layout(N, F, split, &L)) return GH_ERR_INVALID_ARG;
   if (N == 0) return GH_OK;
   if (!points || !verts || !faces || !face_uv || !uv || !workspace) return GH_ERR_INVALID_ARG;
-  if (!ghu_aligned4(points) || !ghu_aligned4(verts) || !ghu_aligned4(faces) || !ghu_aligned4(face_uv) || !ghu_aligned4(uv) ||
-      !ghu_aligned4(dist) || !ghu_aligned4(face) || !ghu_aligned4(bary) || !ghr_al16(workspace))
+  if (!ghr_al4(points) || !ghr_al4(verts) || !ghr_al4(faces) || !ghr_al4(face_uv) || !ghr_al4(uv) ||
+      !ghr_al4(dist) || !ghr_al4(face) || !ghr_al4(bary) || !ghr_al16(workspace))
     return GH_ERR_INVALID_ARG;
   if (ws_bytes < L.total) return GH_ERR_WORKSPACE_SMALL;
   hipStream_t s = (hipStream_t)hip_stream;

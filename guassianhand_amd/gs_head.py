@@ -11,7 +11,7 @@ row stride (a column window of a wider tensor is not copied). Every sum has a fi
 for the weight gradient — and there are no atomics: a row's outputs and its grad_x are bitwise the same alone or among 100,000 rows,
 and weight gradients are bitwise reproducible run to run.
 
-CPU tensors, and `ops="torch"` on any device, go through `_gs_head_ref`: `renderer.gs_activations` over one `F.linear`, in float64 on
+CPU tensors, and `ops="torch"` on any device, go through `gs_head_ref`: `renderer.gs_activations` over one `F.linear`, in float64 on
 request (the yardstick of the GPU tests). ROCm tensors go through the HIP kernels only.
 
 `GSLayer` is the module itself with the reference's state-dict keys (`out_layers.{0..4}.{weight,bias}`) and initialisation, so a
@@ -35,26 +35,39 @@ from ._call import check_f32, check_ops, cotangent, launch, lib, ptr, row_stride
 from .renderer import GaussianModel, gs_activations
 
 FIELDS = ("xyz", "scaling", "rotation", "opacity", "shs")          # the order of the concatenated rows (gh_head.h)
-_FIXED = {"xyz": 3, "scaling": 3, "rotation": 4, "opacity": 1}
+FIXED_WIDTHS = {"xyz": 3, "scaling": 3, "rotation": 4, "opacity": 1}
 SHS_WIDTHS = (3, 12, 27, 48)
+
+
+def head_config(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling) -> tuple:
+    """The head's configuration as the autograd functions carry it and head_desc reads it."""
+    return (int(shs_width), bool(use_rgb), bool(xyz_offset), bool(restrict_offset), None if clip_scaling is None else float(clip_scaling))
+
+
+def check_widths(shs_width, use_rgb, why: str = "") -> None:
+    if int(shs_width) not in SHS_WIDTHS:
+        raise ValueError(f"shs_width must be one of {SHS_WIDTHS}, got {shs_width}")
+    if use_rgb and int(shs_width) != 3:
+        raise ValueError(f"use_rgb needs shs_width = 3{why}, got {shs_width}")
+
+
+def check_pts_and_clip(x, pts, clip_scaling) -> None:
+    if pts.shape[0] != x.shape[0] or pts.shape[1] != 3:
+        raise ValueError(f"pts: expected ({x.shape[0]}, 3) for x {tuple(x.shape)}, got {tuple(pts.shape)}")
+    if clip_scaling is not None and not float(clip_scaling) >= 0:
+        raise ValueError(f"clip_scaling must be >= 0 or None, got {clip_scaling}")
 
 
 def _check(x, pts, weight, bias, shs_width, use_rgb, clip_scaling) -> None:
     """Everything that can be refused on the host is, before any device work."""
     check_f32(x, (("x", x, 2), ("pts", pts, 2), ("weight", weight, 2), ("bias", bias, 1)))
-    if int(shs_width) not in SHS_WIDTHS:
-        raise ValueError(f"shs_width must be one of {SHS_WIDTHS}, got {shs_width}")
-    if use_rgb and int(shs_width) != 3:
-        raise ValueError(f"use_rgb needs shs_width = 3 (the reference builds a 3-channel head under use_rgb), got {shs_width}")
+    check_widths(shs_width, use_rgb, " (the reference builds a 3-channel head under use_rgb)")
     O = 11 + int(shs_width)
     if weight.shape[0] != O or bias.shape[0] != O:
         raise ValueError(f"weight / bias: expected {O} rows (11 + shs_width = {shs_width}) for these flags, got {weight.shape[0]} / {bias.shape[0]}")
     if weight.shape[1] != x.shape[1] or x.shape[1] < 1:
         raise ValueError(f"weight is {tuple(weight.shape)}, x has {x.shape[1]} columns")
-    if pts.shape[0] != x.shape[0] or pts.shape[1] != 3:
-        raise ValueError(f"pts: expected ({x.shape[0]}, 3) for x {tuple(x.shape)}, got {tuple(pts.shape)}")
-    if clip_scaling is not None and not float(clip_scaling) >= 0:
-        raise ValueError(f"clip_scaling must be >= 0 or None, got {clip_scaling}")
+    check_pts_and_clip(x, pts, clip_scaling)
 
 
 # ---- plain-torch restatement (CPU path; the yardstick of the device path) --------------------------------------------------------
@@ -88,8 +101,8 @@ def _activations_keep(raw, pts, use_rgb, xyz_offset, restrict_offset, clip_scali
     return GaussianModel(xyz=xyz, opacity=torch.sigmoid(raw["opacity"]), rotation=F.normalize(raw["rotation"]), scaling=scaling, shs=shs)
 
 
-def _gs_head_ref(x, pts, weight, bias, *, shs_width, use_rgb=False, xyz_offset=True, restrict_offset=False, clip_scaling=None,
-                 acc: Optional[torch.dtype] = None) -> GaussianModel:
+def gs_head_ref(x, pts, weight, bias, *, shs_width, use_rgb=False, xyz_offset=True, restrict_offset=False, clip_scaling=None,
+                acc: Optional[torch.dtype] = None) -> GaussianModel:
     """The head in plain torch, differentiable: gs_activations over one F.linear. acc=torch.float64 computes (and returns) in double."""
     if acc is not None:
         x, pts, weight, bias = (t.to(acc) for t in (x, pts, weight, bias))
@@ -101,11 +114,26 @@ def _gs_head_ref(x, pts, weight, bias, *, shs_width, use_rgb=False, xyz_offset=T
     return _activations_keep(raw, pts, use_rgb, xyz_offset, restrict_offset, clip_scaling)
 
 
+_gs_head_ref = gs_head_ref                                          # the name the tests call it by
+
+
 # ---- device path ---------------------------------------------------------------------------------------------------------------
-def _desc(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling) -> _abi.GhHeadDesc:
+def head_desc(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling) -> _abi.GhHeadDesc:
+    """GhHeadDesc of a head_config."""
     flags = (_abi.GH_HEAD_USE_RGB if use_rgb else 0) | (_abi.GH_HEAD_XYZ_OFFSET if xyz_offset else 0) | \
         (_abi.GH_HEAD_RESTRICT_OFFSET if restrict_offset else 0) | (_abi.GH_HEAD_CLIP_SCALING if clip_scaling is not None else 0)
     return _abi.GhHeadDesc(int(shs_width), flags, 0.0 if clip_scaling is None else float(clip_scaling))
+
+
+def new_outputs(P: int, shs_width: int, device, with_raw: bool):
+    """The five outputs in FIELDS order, uninitialised, and `raw` (P, 11 + shs_width) for the backward, or None."""
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
+    return (new(P, 3), new(P, 3), new(P, 4), new(P, 1), new(P, shs_width)), (new(P, 11 + shs_width) if with_raw else None)
+
+
+def pack(xyz, scaling, rotation, opacity, shs) -> GaussianModel:
+    """The five outputs in FIELDS order -> GaussianModel, shs (P, shs_width) as (P, shs_width / 3, 3)."""
+    return GaussianModel(xyz=xyz, opacity=opacity, rotation=rotation, scaling=scaling, shs=shs.reshape(shs.shape[0], shs.shape[1] // 3, 3))
 
 
 class _GsHeadFn(torch.autograd.Function):
@@ -116,16 +144,13 @@ class _GsHeadFn(torch.autograd.Function):
         x, pts, weight, bias = rows(x.detach()), pts.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
         P, Cin = x.shape
         O, dev = 11 + shs_width, x.device
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        xyz, scaling, rotation, opacity, shs = new(P, 3), new(P, 3), new(P, 4), new(P, 1), new(P, shs_width)
-        raw = new(P, O) if any(ctx.needs_input_grad[:4]) else None
+        outs, raw = new_outputs(P, shs_width, dev, any(ctx.needs_input_grad[:4]))
         if P > 0:
-            launch("gh_head_forward", dev, ptr(x), row_stride(x), P, Cin, ptr(pts), ptr(weight), ptr(bias), C.byref(_desc(*cfg)),
-                   ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(shs), ptr(raw),
-                   what=f"gh_head_forward (P={P}, Cin={Cin}, O={O})")
+            launch("gh_head_forward", dev, ptr(x), row_stride(x), P, Cin, ptr(pts), ptr(weight), ptr(bias), C.byref(head_desc(*cfg)),
+                   *[ptr(o) for o in outs], ptr(raw), what=f"gh_head_forward (P={P}, Cin={Cin}, O={O})")
         ctx.cfg = cfg
         ctx.save_for_backward(x, weight, raw)
-        return xyz, scaling, rotation, opacity, shs
+        return outs
 
     @staticmethod
     @once_differentiable
@@ -145,7 +170,7 @@ class _GsHeadFn(torch.autograd.Function):
             gs = [cotangent(g) for g in (g_xyz, g_scaling, g_rotation, g_opacity, g_shs)]
             nbytes = int(lib().gh_head_workspace_bytes(P, Cin, O)) if need_w else 0
             ws = workspace(nbytes, dev) if need_w else None
-            launch("gh_head_backward", dev, ptr(raw), ptr(x), row_stride(x), P, Cin, ptr(weight), C.byref(_desc(*ctx.cfg)),
+            launch("gh_head_backward", dev, ptr(raw), ptr(x), row_stride(x), P, Cin, ptr(weight), C.byref(head_desc(*ctx.cfg)),
                    *[ptr(g) for g in gs], ptr(gx), Cin, ptr(gpts), ptr(gw), ptr(gb), ptr(ws), nbytes,
                    what=f"gh_head_backward (P={P}, Cin={Cin}, O={O})")
         return (gx if ctx.needs_input_grad[0] else None, gpts, gw if ctx.needs_input_grad[2] else None,
@@ -161,12 +186,11 @@ def gs_head(x: torch.Tensor, pts: torch.Tensor, weight: torch.Tensor, bias: torc
     CPU tensors always take it."""
     check_ops(ops)
     _check(x, pts, weight, bias, shs_width, use_rgb, clip_scaling)
-    cfg = (int(shs_width), bool(use_rgb), bool(xyz_offset), bool(restrict_offset), None if clip_scaling is None else float(clip_scaling))
+    cfg = head_config(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling)
     if ops == "torch" or not x.is_cuda:
-        return _gs_head_ref(x, pts, weight, bias, shs_width=cfg[0], use_rgb=cfg[1], xyz_offset=cfg[2], restrict_offset=cfg[3],
-                            clip_scaling=cfg[4])
-    xyz, scaling, rotation, opacity, shs = _GsHeadFn.apply(x, pts, weight, bias, cfg)
-    return GaussianModel(xyz=xyz, opacity=opacity, rotation=rotation, scaling=scaling, shs=shs.reshape(shs.shape[0], cfg[0] // 3, 3))
+        return gs_head_ref(x, pts, weight, bias, shs_width=cfg[0], use_rgb=cfg[1], xyz_offset=cfg[2], restrict_offset=cfg[3],
+                           clip_scaling=cfg[4])
+    return pack(*_GsHeadFn.apply(x, pts, weight, bias, cfg))
 
 
 # ---- the module ------------------------------------------------------------------------------------------------------------------
@@ -179,7 +203,7 @@ def gs_layer_forward(self, x: torch.Tensor, pts: torch.Tensor, ops: Optional[str
     if sorted(keys) != sorted(FIELDS) or len(self.out_layers) != len(FIELDS):
         raise ValueError(f"feature_channels must name exactly {FIELDS}, got {keys}")
     layers = {k: layer for k, layer in zip(keys, self.out_layers)}
-    for k, n in _FIXED.items():
+    for k, n in FIXED_WIDTHS.items():
         if layers[k].out_features != n:
             raise ValueError(f"the {k} head must have {n} outputs, got {layers[k].out_features}")
     weight = torch.cat([layers[k].weight for k in FIELDS], dim=0)
@@ -236,6 +260,10 @@ class GSLayer(nn.Module):
 _fused_cls = {}
 
 
+def is_fused_cls(cls) -> bool:
+    return cls in _fused_cls.values()
+
+
 def fused_gs_layer_cls(base):
     """A subclass of the given GSLayer class (the reference's own, tgs.models.renderer_one_shot.GSLayer) whose forward is
     gs_layer_forward; configure(), the parameters and the config handling stay the base class's."""
@@ -250,6 +278,6 @@ def fuse_gs_head(renderer):
     """Swap the class of `renderer.gs_net` for fused_gs_layer_cls of its own class: forward_gs then ends in one HIP pass. The module
     object, its parameters and its state dict are untouched. Returns the renderer."""
     net = renderer.gs_net
-    if type(net) not in _fused_cls.values() and not isinstance(net, GSLayer):
+    if not is_fused_cls(type(net)) and not isinstance(net, GSLayer):
         net.__class__ = fused_gs_layer_cls(type(net))
     return renderer

@@ -12,7 +12,7 @@ its row stride. Every sum has a fixed order that depends on the sizes alone, and
 are bitwise the same alone or among 100,000 rows.
 
 CPU tensors, and `ops="torch"` on any device, go through `_gs_trunk_ref`: F.linear and F.silu / F.relu three times, then
-gs_head._gs_head_ref, in float64 on request (the yardstick of the GPU tests), differentiable with respect to everything.
+gs_head.gs_head_ref, in float64 on request (the yardstick of the GPU tests), differentiable with respect to everything.
 
 `TrunkMLP` is the trunk as a module with the reference's state-dict keys (`layers.{0,2,4}.{weight,bias}` for two hidden layers) and
 nn.Linear's initialisation. `forward_gs_fused(renderer, x, p)` is forward_gs with the kernel where `kernel_args` finds it applicable
@@ -30,7 +30,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _abi, gs_head
 from ._call import check_f32, check_ops, cotangent, launch, ptr, row_stride, rows
-from .gs_head import _FIXED, FIELDS, SHS_WIDTHS, _desc, _gs_head_ref
+from .gs_head import FIELDS, FIXED_WIDTHS, SHS_WIDTHS, check_pts_and_clip, check_widths, gs_head_ref, head_config, head_desc, new_outputs, pack
 from .renderer import GaussianModel
 
 ACTIVATIONS = {"silu": _abi.GH_TRUNK_SILU, "relu": _abi.GH_TRUNK_RELU}
@@ -51,10 +51,7 @@ def _check(x, pts, trunk, head_weight, head_bias, shs_width, use_rgb, clip_scali
                   ("head_weight", head_weight, 2), ("head_bias", head_bias, 1)))
     if activation not in ACTIVATIONS:
         raise ValueError(f"activation must be one of {tuple(ACTIVATIONS)}, got {activation!r}")
-    if int(shs_width) not in SHS_WIDTHS:
-        raise ValueError(f"shs_width must be one of {SHS_WIDTHS}, got {shs_width}")
-    if use_rgb and int(shs_width) != 3:
-        raise ValueError(f"use_rgb needs shs_width = 3, got {shs_width}")
+    check_widths(shs_width, use_rgb)
     H, Cout, O = W1.shape[0], W3.shape[0], 11 + int(shs_width)
     if W1.shape[1] != x.shape[1] or x.shape[1] < 1:
         raise ValueError(f"W1 is {tuple(W1.shape)}, x has {x.shape[1]} columns")
@@ -64,10 +61,7 @@ def _check(x, pts, trunk, head_weight, head_bias, shs_width, use_rgb, clip_scali
     if tuple(head_weight.shape) != (O, Cout) or head_bias.shape[0] != O:
         raise ValueError(f"head_weight / head_bias: expected ({O}, {Cout}) and ({O},) (11 + shs_width = {shs_width} rows), got "
                          f"{tuple(head_weight.shape)} / {tuple(head_bias.shape)}")
-    if pts.shape[0] != x.shape[0] or pts.shape[1] != 3:
-        raise ValueError(f"pts: expected ({x.shape[0]}, 3) for x {tuple(x.shape)}, got {tuple(pts.shape)}")
-    if clip_scaling is not None and not float(clip_scaling) >= 0:
-        raise ValueError(f"clip_scaling must be >= 0 or None, got {clip_scaling}")
+    check_pts_and_clip(x, pts, clip_scaling)
 
 
 # ---- plain-torch restatement (CPU path; the yardstick of the device path) --------------------------------------------------------
@@ -81,8 +75,8 @@ def _gs_trunk_ref(x, pts, trunk: Sequence[torch.Tensor], head_weight, head_bias,
     W1, b1, W2, b2, W3, b3 = trunk
     act = F.silu if activation == "silu" else F.relu
     y = F.linear(act(F.linear(act(F.linear(x, W1, b1)), W2, b2)), W3, b3)
-    return _gs_head_ref(y, pts, head_weight, head_bias, shs_width=shs_width, use_rgb=use_rgb, xyz_offset=xyz_offset,
-                        restrict_offset=restrict_offset, clip_scaling=clip_scaling)
+    return gs_head_ref(y, pts, head_weight, head_bias, shs_width=shs_width, use_rgb=use_rgb, xyz_offset=xyz_offset,
+                       restrict_offset=restrict_offset, clip_scaling=clip_scaling)
 
 
 # ---- device path ---------------------------------------------------------------------------------------------------------------
@@ -96,16 +90,14 @@ class _GsTrunkFn(torch.autograd.Function):
         W1, _, _, _, W3, _, Wh, _ = weights
         P, Cin = x.shape
         H, Cout, O, dev = W1.shape[0], W3.shape[0], 11 + shs_width, x.device
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        xyz, scaling, rotation, opacity, shs = new(P, 3), new(P, 3), new(P, 4), new(P, 1), new(P, shs_width)
-        raw = new(P, O) if any(ctx.needs_input_grad[:2]) else None
+        outs, raw = new_outputs(P, shs_width, dev, any(ctx.needs_input_grad[:2]))
         if P > 0:
             launch("gh_trunk_forward", dev, ptr(x), row_stride(x), P, Cin, H, Cout, ptr(pts), *[ptr(w) for w in weights],
-                   C.byref(_desc(*cfg)), ACTIVATIONS[activation], ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(shs), ptr(raw),
+                   C.byref(head_desc(*cfg)), ACTIVATIONS[activation], *[ptr(o) for o in outs], ptr(raw),
                    what=f"gh_trunk_forward (P={P}, Cin={Cin}, H={H}, Cout={Cout}, O={O})")
         ctx.cfg, ctx.activation = cfg, activation
         ctx.save_for_backward(x, raw, *weights)
-        return xyz, scaling, rotation, opacity, shs
+        return outs
 
     @staticmethod
     @once_differentiable
@@ -118,7 +110,7 @@ class _GsTrunkFn(torch.autograd.Function):
         if P > 0:
             gs = [cotangent(g) for g in (g_xyz, g_scaling, g_rotation, g_opacity, g_shs)]
             launch("gh_trunk_backward", dev, ptr(raw), ptr(x), row_stride(x), P, Cin, H, Cout, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(W3),
-                   ptr(Wh), C.byref(_desc(*ctx.cfg)), ACTIVATIONS[ctx.activation], *[ptr(g) for g in gs], ptr(gx), Cin, ptr(gpts),
+                   ptr(Wh), C.byref(head_desc(*ctx.cfg)), ACTIVATIONS[ctx.activation], *[ptr(g) for g in gs], ptr(gx), Cin, ptr(gpts),
                    what=f"gh_trunk_backward (P={P}, Cin={Cin}, H={H}, Cout={Cout}, O={Wh.shape[0]})")
         return (gx if ctx.needs_input_grad[0] else None, gpts, None, None) + (None,) * 8
 
@@ -133,7 +125,7 @@ def gs_trunk(x: torch.Tensor, pts: torch.Tensor, trunk: Sequence[torch.Tensor], 
     check_ops(ops)
     trunk = tuple(trunk)
     _check(x, pts, trunk, head_weight, head_bias, shs_width, use_rgb, clip_scaling, activation)
-    cfg = (int(shs_width), bool(use_rgb), bool(xyz_offset), bool(restrict_offset), None if clip_scaling is None else float(clip_scaling))
+    cfg = head_config(shs_width, use_rgb, xyz_offset, restrict_offset, clip_scaling)
     if ops == "torch" or not x.is_cuda:
         return _gs_trunk_ref(x, pts, trunk, head_weight, head_bias, shs_width=cfg[0], use_rgb=cfg[1], xyz_offset=cfg[2],
                              restrict_offset=cfg[3], clip_scaling=cfg[4], activation=activation)
@@ -142,8 +134,7 @@ def gs_trunk(x: torch.Tensor, pts: torch.Tensor, trunk: Sequence[torch.Tensor], 
         raise ValueError(f"the trunk kernels take 1 <= Cin <= {MAX_CIN} and H, Cout in {WIDTHS}, got Cin={Cin}, H={H}, Cout={Cout}")
     if torch.is_grad_enabled() and any(w.requires_grad for w in (*trunk, head_weight, head_bias)):
         raise RuntimeError("the trunk kernels produce no gradient of a weight: freeze the trunk and the head, or use ops='torch'")
-    xyz, scaling, rotation, opacity, shs = _GsTrunkFn.apply(x, pts, cfg, activation, *trunk, head_weight, head_bias)
-    return GaussianModel(xyz=xyz, opacity=opacity, rotation=rotation, scaling=scaling, shs=shs.reshape(shs.shape[0], cfg[0] // 3, 3))
+    return pack(*_GsTrunkFn.apply(x, pts, cfg, activation, *trunk, head_weight, head_bias))
 
 
 # ---- the module ------------------------------------------------------------------------------------------------------------------
@@ -180,7 +171,7 @@ def _forward_is_gslayers(net) -> bool:
     """Whether net(x, p) is GSLayer.forward — the reference's own, gs_head.GSLayer's or the fused head's — which the kernels restate.
     A subclass with a forward of its own keeps it: the kernels would replace it silently."""
     owner = next((c for c in type(net).__mro__ if "forward" in vars(c)), None)
-    return owner is gs_head.GSLayer or owner in gs_head._fused_cls.values() or (getattr(owner, "__module__", None), getattr(owner, "__name__", None)) in _REFERENCE_HEADS
+    return owner is gs_head.GSLayer or gs_head.is_fused_cls(owner) or (getattr(owner, "__module__", None), getattr(owner, "__name__", None)) in _REFERENCE_HEADS
 
 
 def kernel_args(renderer, x, p):
@@ -209,7 +200,7 @@ def kernel_args(renderer, x, p):
     if heads is None or len(heads) != len(FIELDS) or sorted(keys) != sorted(FIELDS) or not _forward_is_gslayers(net):
         return None
     by_key = dict(zip(keys, heads))
-    if not all(isinstance(l, nn.Linear) and l.bias is not None for l in heads) or any(by_key[k].out_features != n for k, n in _FIXED.items()):
+    if not all(isinstance(l, nn.Linear) and l.bias is not None for l in heads) or any(by_key[k].out_features != n for k, n in FIXED_WIDTHS.items()):
         return None
     width, use_rgb = by_key["shs"].out_features, bool(hcfg.use_rgb)
     if not sizes_supported(l1.in_features, l1.out_features, l3.out_features, width) or (use_rgb and width != 3):
