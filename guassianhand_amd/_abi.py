@@ -498,12 +498,37 @@ def declare_trunk(lib: C.CDLL) -> None:
     lib.gh_trunk_backward.argtypes = [V, V, L, I, I, I, I] + [V] * 6 + [D, I] + [V] * 5 + [V, L, V, V]
 
 
+# ---- include/gh_conv.h: the perceptual loss's 3x3 convolution and 2x2 max pooling (a header of its own, as gh_trunk.h is) ----
+GH_CONV_RELU = 1
+GH_CONV_MAX_C = 512
+GH_CONV_PIXELS = 128
+GH_CONV_CHUNK = 128
+GH_CONV_FILL = 512
+
+CONV_SYMBOLS = ("gh_conv3x3_weight_floats", "gh_conv3x3_forward", "gh_conv3x3_backward_data", "gh_maxpool2x2_forward", "gh_maxpool2x2_backward")
+
+
+def declare_conv(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_conv.h declares."""
+    V, I, U = C.c_void_p, C.c_int, C.c_uint32
+    lib.gh_conv3x3_weight_floats.restype = C.c_size_t
+    lib.gh_conv3x3_weight_floats.argtypes = [I, I]
+    lib.gh_conv3x3_forward.restype = C.c_int
+    lib.gh_conv3x3_forward.argtypes = [V, I, I, I, I, I, V, V, U, I, V, V, V]
+    lib.gh_conv3x3_backward_data.restype = C.c_int
+    lib.gh_conv3x3_backward_data.argtypes = [V, V, I, I, I, I, I, V, U, I, V, V]
+    lib.gh_maxpool2x2_forward.restype = C.c_int
+    lib.gh_maxpool2x2_forward.argtypes = [V, I, I, I, I, V, V, V]
+    lib.gh_maxpool2x2_backward.restype = C.c_int
+    lib.gh_maxpool2x2_backward.argtypes = [V, V, I, I, I, I, V, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the thirteen headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the fourteen headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows, declare_scene, declare_trunk):
+                declare_attn_rows, declare_scene, declare_trunk, declare_conv):
         one(lib)

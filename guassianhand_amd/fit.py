@@ -7,8 +7,10 @@ What it mirrors (all in /root/reference):
   * per-Gaussian lookup of the maps at the Gaussians' UV coordinates with bilinear `grid_sample`,
     align_corners=True — renderer_one_shot.py:420-446, :489-492;
   * loss: 10 * L1(rgb) + 1.0 * MSE(clip(mean_c(mask), -0.001, 1), gt_mask) — utils.py:180-252, :282-291 with the
-    shipped lambdas (config/one_shot.json:121-132; the 0.1*VGG term needs torchvision weights and is out of scope)
-    — plus the regularisers 100*mean|color_b| + mean(opacity_b^2) — infer_one_shot.py:514-519;
+    shipped lambdas (config/one_shot.json:121-132) — plus, with `perceptual=` given, lambda_vgg (0.1) * VGGLoss of the
+    bbox-zeroed render against gt_rgb (utils.py:255-278, :910-930; guassianhand_amd.perceptual — its weights are the
+    reference checkpoint's own `vgg_loss.vgg_net.*`) — plus the regularisers
+    100*mean|color_b| + mean(opacity_b^2) — infer_one_shot.py:514-519;
   * optimiser: Adam(lr 0.01) + MultiStepLR(milestones [2,5,10,20,35,50,75], gamma 0.5) per epoch — :345-349,
     config/one_shot.json:29.
 
@@ -65,8 +67,13 @@ def fit_loss(comp_rgb, comp_mask, gt_rgb, gt_mask, bbox_mask=None, lambda_l1: fl
 class OneShotFit(nn.Module):
     def __init__(self, gs: GaussianModel, uv: torch.Tensor, *, use_rgb: bool = True, sh_degree: int = 3,
                  map_hw: Sequence[int] = (1024, 2048), lr: float = 0.01, render_fn: Optional[Callable] = None,
-                 active_texels: Optional[bool] = None, static_geometry: Optional[bool] = None, occlusion_bound: bool = False):
+                 active_texels: Optional[bool] = None, static_geometry: Optional[bool] = None, occlusion_bound: bool = False,
+                 perceptual: Optional[nn.Module] = None, lambda_vgg: float = 0.1):
         super().__init__()
+        # The perceptual term (a guassianhand_amd.perceptual.PerceptualLoss; None: the step takes the paths it took without one).
+        # It is held outside the module tree: its frozen network is no state of the fit.
+        object.__setattr__(self, "perceptual", perceptual)
+        self.lambda_vgg, self._vgg_target = float(lambda_vgg), None
         self.gs = GaussianModel(*[t.detach() for t in gs])          # frozen network outputs
         self.register_buffer("uv", uv.detach().float())
         self.use_rgb, self.sh_degree = use_rgb, sh_degree
@@ -211,6 +218,21 @@ class OneShotFit(nn.Module):
                               color_b=blend["color_b"], opacity_b=blend["opacity_b"], use_rgb=self.use_rgb,
                               sh_degree=self.sh_degree, sync=sync, **kw)
 
+    def _perceptual_term(self, out, gt_rgb, bbox_mask, mine, n_total: int) -> torch.Tensor:
+        """lambda_vgg * len(mine) / n_total * VGGLoss(bbox-zeroed render, gt_rgb) of this rank's views (utils.py:255-278,
+        infer_one_shot.py:503-507): the ranks' terms add up to the loss over all views when they hold equally many. The target's
+        feature maps are computed once per gt_rgb tensor and version."""
+        image = out["image_chw"] if "image_chw" in out else out["comp_rgb"].permute(0, 3, 1, 2)
+        if bbox_mask is not None:
+            bb = bbox_mask if len(mine) == n_total else bbox_mask[mine]
+            image = image * (bb[:, None] != 0)
+        key = (gt_rgb._version, tuple(mine))
+        tg = self._vgg_target
+        if tg is None or tg[0] is not gt_rgb or tg[1] != key:
+            tgt = gt_rgb if len(mine) == n_total else gt_rgb[mine]
+            self._vgg_target = tg = (gt_rgb, key, self.perceptual.target_features(tgt.permute(0, 3, 1, 2).float()))
+        return (self.lambda_vgg * len(mine) / n_total) * self.perceptual(image, target_features=tg[2])
+
     def _is_depth_bound_cache(self) -> bool:
         return isinstance(self._geom_cache, R.DepthBoundCache)
 
@@ -244,7 +266,7 @@ class OneShotFit(nn.Module):
             allv = len(mine) == n_total
             sel = (lambda t: t) if len(mine) == n_total else (lambda t: t[mine])
             out = None
-            if self._default_render and self.color_w.is_cuda and allv:
+            if self._default_render and self.color_w.is_cuda and allv and self.perceptual is None:
                 # render + image loss as ONE autograd node (loss.rendered_fit_loss): dL/dloss is applied inside the render
                 # backward instead of in two elementwise passes over the images
                 from .loss import rendered_fit_loss
@@ -275,6 +297,8 @@ class OneShotFit(nn.Module):
             else:
                 loss_img = fit_loss(out["comp_rgb"], out["comp_mask"], sel(gt_rgb), sel(gt_mask),
                                     None if bbox_mask is None else sel(bbox_mask)) / n_total
+            if out is not None and self.perceptual is not None:
+                loss_img = loss_img + self._perceptual_term(out, gt_rgb, bbox_mask, mine, n_total)
             if self._one is None or self._one.device != loss_img.device:
                 self._one = torch.ones((), dtype=torch.float32, device=loss_img.device)
             g = torch.autograd.grad(loss_img, [leaves[k] for k in names], grad_outputs=self._one, allow_unused=True)
@@ -361,6 +385,8 @@ class OneShotFit(nn.Module):
 
     def captured(self, w2cs, Ks, H: int, W: int, bg, gt_rgb, gt_mask, bbox_mask=None) -> "CapturedFitStep":
         """The step on these (fixed) cameras and targets as a replayable HIP graph: see CapturedFitStep."""
+        if self.perceptual is not None:
+            raise NotImplementedError("OneShotFit.captured: a fit with a perceptual term is not captured in a HIP graph; call step()")
         return CapturedFitStep(self, (w2cs, Ks, H, W, bg, gt_rgb, gt_mask, bbox_mask))
 
 
