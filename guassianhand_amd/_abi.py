@@ -523,12 +523,57 @@ def declare_conv(lib: C.CDLL) -> None:
     lib.gh_maxpool2x2_backward.argtypes = [V, V, I, I, I, I, V, V]
 
 
+# ---- include/gh_mano.h: the hand points, skinning and folded subdivision (a header of its own, as gh_conv.h is) ----
+GH_MANO_MAX_H = 4
+GH_MANO_MAX_J = 16
+GH_MANO_MAX_NB = 16
+GH_MANO_MAX_LEVELS = 3
+GH_MANO_MAX_V = 65536
+GH_MANO_MAX_P = 4194304
+GH_MANO_MAX_B = 65535
+GH_MANO_CHUNK = 4096
+
+MANO_SYMBOLS = ("gh_mano_workspace_bytes", "gh_mano_forward", "gh_mano_backward")
+MANO_MODEL_ARRAYS = ("v_template", "shapedirs", "posedirs", "lbs_weights", "j_template", "j_shapedirs", "pose_mean", "st_idx", "st_w",
+                     "tr_ptr", "tr_point", "tr_w")
+MANO_PARAMS = ("global_orient", "hand_pose", "betas", "transl")
+
+
+class GhManoDims(C.Structure):
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("J", C.c_int32), ("NB", C.c_int32)]
+
+
+class GhManoModel(C.Structure):
+    """One hand model: the sizes, `parents` in the struct itself, then the device arrays in the header's layouts."""
+    _fields_ = [("V", C.c_int32), ("P", C.c_int32), ("levels", C.c_int32), ("nnz", C.c_int32), ("parents", C.c_int32 * GH_MANO_MAX_J)] + \
+        [(n, C.c_void_p) for n in MANO_MODEL_ARRAYS]
+
+
+class GhManoParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MANO_PARAMS]
+
+
+class GhManoGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MANO_PARAMS]
+
+
+def declare_mano(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_mano.h declares."""
+    D, M, V = C.POINTER(GhManoDims), C.POINTER(GhManoModel), C.c_void_p
+    lib.gh_mano_workspace_bytes.restype = C.c_size_t
+    lib.gh_mano_workspace_bytes.argtypes = [D, M]
+    lib.gh_mano_forward.restype = C.c_int
+    lib.gh_mano_forward.argtypes = [D, M, C.POINTER(GhManoParams), V, V, V, C.c_size_t, V]
+    lib.gh_mano_backward.restype = C.c_int
+    lib.gh_mano_backward.argtypes = [D, M, V, V, C.POINTER(GhManoGrads), V, C.c_size_t, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS + MANO_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the fourteen headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the fifteen headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows, declare_scene, declare_trunk, declare_conv):
+                declare_attn_rows, declare_scene, declare_trunk, declare_conv, declare_mano):
         one(lib)
