@@ -568,12 +568,72 @@ def declare_mano(lib: C.CDLL) -> None:
     lib.gh_mano_backward.argtypes = [D, M, V, V, C.POINTER(GhManoGrads), V, C.c_size_t, V]
 
 
+# ---- include/gh_xf.h: the Transformer1D backbones' forward (a header of its own, as gh_mano.h is) ----
+GH_XF_ROWS = 64
+GH_XF_COLS = 64
+GH_XF_ATTN_ROWS = 64
+GH_XF_ATTN_KEYS = 64
+GH_XF_GN_CHUNK = 256
+GH_XF_MAX_M = 1024
+GH_XF_MAX_C = 1024
+GH_XF_MAX_K = 4096
+GH_XF_MAX_N_OUT = 8192
+GH_XF_MAX_T = 1 << 30
+GH_XF_PRO_NONE, GH_XF_PRO_LN, GH_XF_PRO_GN = 0, 1, 2
+GH_XF_EPI_PLAIN, GH_XF_EPI_BIAS_RES, GH_XF_EPI_GEGLU, GH_XF_EPI_BIAS_RES_CF = 0, 1, 2, 3
+
+XF_SYMBOLS = ("gh_xf_linear_workspace_bytes", "gh_xf_linear", "gh_xf_group_moments_workspace_bytes", "gh_xf_group_moments", "gh_xf_attention",
+              "gh_xf_workspace_bytes", "gh_xf_forward")
+XF_STEM = ("gn_w", "gn_b", "in_w", "in_b", "out_w", "out_b")
+XF_LAYER = ("ln1_w", "ln1_b", "qkv1", "o1_w", "o1_b", "ln2_w", "ln2_b", "qkv2", "o2_w", "o2_b", "ln3_w", "ln3_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b")
+
+
+class GhXfLinear(C.Structure):
+    _fields_ = [("T", C.c_int32), ("K", C.c_int32), ("N_out", C.c_int32), ("prologue", C.c_int32), ("epilogue", C.c_int32),
+                ("rows_per_batch", C.c_int32), ("groups", C.c_int32), ("eps", C.c_float),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("x_stride_b", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("moments", C.c_void_p),
+                ("res", C.c_void_p), ("res_stride", C.c_int64), ("res_stride_b", C.c_int64),
+                ("y", C.c_void_p), ("y_stride", C.c_int64), ("y_stride_b", C.c_int64)]
+
+
+class GhXfDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "C", "N", "G", "heads", "D", "layers")] + [("gn_eps", C.c_float), ("ln_eps", C.c_float)]
+
+
+class GhXfStem(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in XF_STEM]
+
+
+class GhXfLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in XF_LAYER]
+
+
+def declare_xf(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_xf.h declares."""
+    V, I, L = C.c_void_p, C.c_int, C.c_int64
+    lib.gh_xf_linear_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_linear_workspace_bytes.argtypes = [I, I]
+    lib.gh_xf_linear.restype = C.c_int
+    lib.gh_xf_linear.argtypes = [C.POINTER(GhXfLinear), V, C.c_size_t, V]
+    lib.gh_xf_group_moments_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_group_moments_workspace_bytes.argtypes = [I, I, I, I]
+    lib.gh_xf_group_moments.restype = C.c_int
+    lib.gh_xf_group_moments.argtypes = [V, L, L, I, I, I, I, V, V, C.c_size_t, V]
+    lib.gh_xf_attention.restype = C.c_int
+    lib.gh_xf_attention.argtypes = [V, L, I, I, I, I, V, L, V]
+    lib.gh_xf_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_workspace_bytes.argtypes = [C.POINTER(GhXfDims)]
+    lib.gh_xf_forward.restype = C.c_int
+    lib.gh_xf_forward.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStem), C.POINTER(GhXfLayer), V, V, V, C.c_size_t, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS + MANO_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS + MANO_SYMBOLS + XF_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the fifteen headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the sixteen headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows, declare_scene, declare_trunk, declare_conv, declare_mano):
+                declare_attn_rows, declare_scene, declare_trunk, declare_conv, declare_mano, declare_xf):
         one(lib)

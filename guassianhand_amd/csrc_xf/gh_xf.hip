@@ -1,0 +1,667 @@
+// gh_xf.hip — the Transformer1D backbones' forward (include/gh_xf.h): the LDS-tiled product with its prologues and epilogues, the
+// LayerNorm and GroupNorm moments, the streaming-softmax attention for D = 32 and 64, and the host loop that enqueues a whole
+// backbone. Exact float32 MFMA, no atomics, no workgroup that waits for another.
+//
+// The product shape is gh_rows.h's "columns" turned round: v_mfma_f32_32x32x2_f32 with the ROW of X as the A operand's i and the
+// output channel as the B operand's j, so that lane l holds channel j = l & 31 of the rows ghr_acc_row(r, l >> 5) and a register's
+// store is a 128-byte run of one output row per half wave. Both operands cross LDS at the odd pitch 33: lane = row of the tile
+// reads without a bank conflict. The attention keeps gh_attn.hip's shape (the query on the lane, keys and values from LDS).
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/gh_xf.h"
+#include "../csrc_rows/gh_rows.h"
+
+#define GX_TR GH_XF_ROWS
+#define GX_TC GH_XF_COLS
+#define GX_KS 32                   // columns of X and W per slab
+#define GX_P 33                    // LDS pitch of a slab
+#define GX_LN_ROWS (GHR_BLOCK / 64)  // rows per workgroup of the LayerNorm moments: one wave each
+
+static_assert(GHR_BLOCK == 256 && GX_TR == 64 && GX_TC == 64, "four waves, 2 x 2 tiles of 32 x 32; GhrSlab<2, 8> is 64 rows x 32 columns");
+static_assert(GH_XF_GN_CHUNK == GHR_BLOCK, "one position per thread in stage one of the group moments");
+static_assert(GH_XF_ATTN_ROWS == 64 && GH_XF_ATTN_KEYS == 64, "two waves per 32 queries, one per 32 keys of a stage");
+
+__device__ __forceinline__ ghr_acc gx_splat(float v) {
+  ghr_acc z;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[r] = v;
+  return z;
+}
+
+// the 64 lanes' shares in the fixed order xor 32, 16, 8, 4, 2, 1: every lane ends with the same sum
+__device__ __forceinline__ float gx_wave_sum(float s) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+  return s;
+}
+
+// ---- LayerNorm moments: one wave per row -------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_row_moments_kernel(const float* __restrict__ x, long long stride, int T, int K, float eps,
+                                                                    float* __restrict__ mom) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long row = (long long)blockIdx.x * GX_LN_ROWS + wave;
+  if (row >= T) return;                                        // wave-uniform; the kernel has no barrier
+  const float* xr = x + row * stride;
+  float s = 0.f;
+  for (int k = lane; k < K; k += 64) s += xr[k];
+  const float mean = gx_wave_sum(s) / (float)K;
+  float q = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float d = xr[k] - mean;
+    q = fmaf(d, d, q);
+  }
+  const float m2 = gx_wave_sum(q);
+  if (lane == 0) {
+    mom[2 * row] = mean;
+    mom[2 * row + 1] = 1.0f / sqrtf(m2 / (float)K + eps);
+  }
+}
+
+// ---- GroupNorm moments -----------------------------------------------------------------------------------------------------------
+// the workgroup's sum of one value per thread: the wave butterfly, then (s0 + s1) + (s2 + s3). Two barriers; every thread calls it.
+__device__ __forceinline__ float gx_block_sum(float v, float* s_red) {
+  const float w = gx_wave_sum(v);
+  __syncthreads();                                             // the previous call's readers are done
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_group_part_kernel(const float* __restrict__ x, long long stride_b, long long stride_c, int N,
+                                                                   int G, int cpg, int nchunks, float* __restrict__ part) {
+  __shared__ float s_red[4];
+  const int chunk = blockIdx.x % nchunks, bg = blockIdx.x / nchunks, b = bg / G, g = bg - b * G;
+  const int n = chunk * GH_XF_GN_CHUNK + threadIdx.x;
+  const int len = N - chunk * GH_XF_GN_CHUNK < GH_XF_GN_CHUNK ? N - chunk * GH_XF_GN_CHUNK : GH_XF_GN_CHUNK;
+  const float* xp = x + (long long)b * stride_b + (long long)g * cpg * stride_c + n;
+  const bool live = n < N;
+  float s = 0.f;
+  if (live) {
+    for (int c = 0; c < cpg; ++c) s += xp[c * stride_c];
+  }
+  const float mean = gx_block_sum(s, s_red) / ((float)cpg * (float)len);
+  float q = 0.f;
+  if (live) {
+    for (int c = 0; c < cpg; ++c) {
+      const float d = xp[c * stride_c] - mean;
+      q = fmaf(d, d, q);
+    }
+  }
+  const float m2 = gx_block_sum(q, s_red);
+  if (threadIdx.x == 0) {
+    part[2 * (long long)blockIdx.x] = mean;
+    part[2 * (long long)blockIdx.x + 1] = m2;
+  }
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_group_join_kernel(const float* __restrict__ part, int BG, int N, int cpg, int nchunks,
+                                                                   float* __restrict__ mom) {
+  const int bg = blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (bg >= BG) return;
+  const float* p = part + 2 * (long long)bg * nchunks;
+  float mean = p[0], m2 = p[1];
+  float na = (float)cpg * (float)(N < GH_XF_GN_CHUNK ? N : GH_XF_GN_CHUNK);
+  for (int c = 1; c < nchunks; ++c) {
+    const int len = N - c * GH_XF_GN_CHUNK < GH_XF_GN_CHUNK ? N - c * GH_XF_GN_CHUNK : GH_XF_GN_CHUNK;
+    const float nc = (float)cpg * (float)len, n = na + nc, delta = p[2 * c] - mean;
+    mean = mean + (delta * nc) / n;
+    m2 = (m2 + p[2 * c + 1]) + ((delta * delta) * na) * nc / n;
+    na = n;
+  }
+  mom[2 * bg] = mean;
+  mom[2 * bg + 1] = m2;
+}
+
+// ---- the product ---------------------------------------------------------------------------------------------------------------------
+// One slab of X on its way into LDS. PRO_NONE and PRO_LN: gh_rows.h's window, element (r, c) = X[row0 + r][k0 + c], thread i moves
+// rows i / 8 and (i + 256) / 8. PRO_GN: X is channel first, so consecutive threads take consecutive rows: thread i owns tile row
+// i & 63 and the wave-uniform columns (i >> 6) + 4 it.
+template <int PRO>
+struct GxSlabX {
+  GhrSlab<2, 8> w;
+  float g[8];
+};
+
+template <int PRO>
+__device__ __forceinline__ void gx_fetch_x(GxSlabX<PRO>& t, const GhXfLinear& a, int row0, int k0, int vec, long long gn_base, bool gn_live,
+                                           int tid) {
+  if constexpr (PRO == GH_XF_PRO_GN) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) t.g[it] = gn_live ? a.x[gn_base + (long long)(k0 + (tid >> 6) + 4 * it) * a.x_stride] : 0.f;
+  } else {
+    ghr_fetch_in(t.w, a.x, a.x_stride, row0, k0, a.T, a.K, vec, tid);
+  }
+}
+
+// what gx_fetch_x brought, through the prologue, into s_x. ln: {mean, rstd} of the thread's two rows; gn_mom: the thread's batch
+// element's moments.
+template <int PRO>
+__device__ __forceinline__ void gx_put_x(const GxSlabX<PRO>& t, float* s_x, const GhXfLinear& a, int k0, const float (&ln)[2][2],
+                                         const float* __restrict__ gn_mom, int cpg, float gn_cnt, int tid) {
+  if constexpr (PRO == GH_XF_PRO_GN) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int kk = (tid >> 6) + 4 * it, c = k0 + kk, g = c / cpg;
+      const float mean = gn_mom ? gn_mom[2 * g] : 0.f, m2 = gn_mom ? gn_mom[2 * g + 1] : 0.f;
+      const float rstd = 1.0f / sqrtf(m2 / gn_cnt + a.eps);
+      s_x[(tid & 63) * GX_P + kk] = ((t.g[it] - mean) * rstd) * a.gamma[c] + a.beta[c];
+    }
+  } else {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int i = tid + it * GHR_BLOCK, r = i / 8, c = 4 * (i % 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float v = t.w.v[it][j];
+        if constexpr (PRO == GH_XF_PRO_LN) v = ((v - ln[it][0]) * ln[it][1]) * a.gamma[k0 + c + j] + a.beta[k0 + c + j];
+        s_x[r * GX_P + c + j] = v;
+      }
+    }
+  }
+}
+
+template <int PRO, int EPI>
+__global__ __launch_bounds__(GHR_BLOCK) void gx_linear_kernel(GhXfLinear a, const float* __restrict__ ln_mom, int vec_x, int vec_w,
+                                                               int ncol_tiles) {
+  constexpr int NB = EPI == GH_XF_EPI_GEGLU ? 2 : 1;
+  __shared__ float s_all[GX_TR * GX_P + NB * GX_TC * GX_P];    // X slab, NB W slabs; the channel-first epilogue's four 32 x 33 tiles
+  static_assert(GX_TR * GX_P + GX_TC * GX_P >= 4 * 32 * GX_P, "the slabs double as the four waves' transpose tiles");
+  float* s_x = s_all;
+  float* s_w = s_all + GX_TR * GX_P;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int tc = blockIdx.x % ncol_tiles, tr = blockIdx.x / ncol_tiles;
+  const int row0 = tr * GX_TR, c0 = tc * GX_TC;
+  const int N = a.rows_per_batch;
+
+  float ln[2][2] = {{0.f, 1.f}, {0.f, 1.f}};
+  if constexpr (PRO == GH_XF_PRO_LN) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int r = row0 + (tid + it * GHR_BLOCK) / 8;
+      if (r < a.T) {
+        ln[it][0] = ln_mom[2 * (long long)r];
+        ln[it][1] = ln_mom[2 * (long long)r + 1];
+      }
+    }
+  }
+  long long gn_base = 0;
+  bool gn_live = false;
+  const float* gn_mom = nullptr;
+  int cpg = 1;
+  float gn_cnt = 1.f;
+  if constexpr (PRO == GH_XF_PRO_GN) {
+    const int t = row0 + (tid & 63);
+    gn_live = t < a.T;
+    const int b = gn_live ? t / N : 0, n = gn_live ? t - b * N : 0;
+    gn_base = (long long)b * a.x_stride_b + n;
+    cpg = a.K / a.groups;
+    gn_cnt = (float)cpg * (float)N;
+    gn_mom = gn_live ? a.moments + 2 * (long long)b * a.groups : nullptr;
+  }
+
+  const int j = c0 + 32 * wc + col;                            // the lane's output channel
+  ghr_acc acc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    float bv = 0.f;
+    if (EPI != GH_XF_EPI_PLAIN && a.bias && j < a.N_out) bv = a.bias[(long long)b * a.N_out + j];
+    acc[b] = gx_splat(bv);
+  }
+
+  GxSlabX<PRO> xs;
+  GhrSlab<2, 8> ws[NB];
+  gx_fetch_x<PRO>(xs, a, row0, 0, vec_x, gn_base, gn_live, tid);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) ghr_fetch_in(ws[b], a.w + (long long)b * a.N_out * a.K, a.K, c0, 0, a.N_out, a.K, vec_w, tid);
+  for (int k0 = 0; k0 < a.K; k0 += GX_KS) {
+    __syncthreads();                                           // the previous slab has been read by every wave
+    gx_put_x<PRO>(xs, s_x, a, k0, ln, gn_mom, cpg, gn_cnt, tid);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) ghr_put(ws[b], s_w + b * GX_TC * GX_P, GX_P, tid);
+    __syncthreads();
+    if (k0 + GX_KS < a.K) {                                    // the next slab's loads fly under this slab's products
+      gx_fetch_x<PRO>(xs, a, row0, k0 + GX_KS, vec_x, gn_base, gn_live, tid);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) ghr_fetch_in(ws[b], a.w + (long long)b * a.N_out * a.K, a.K, c0, k0 + GX_KS, a.N_out, a.K, vec_w, tid);
+    }
+    const float* ap = s_x + (32 * wr + col) * GX_P + half;
+    const float* bp = s_w + (32 * wc + col) * GX_P + half;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float av = ap[2 * s];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[b * GX_TC * GX_P + 2 * s], acc[b], 0, 0, 0);
+    }
+  }
+
+  if constexpr (EPI == GH_XF_EPI_BIAS_RES_CF) {
+    // the wave's tile crosses LDS so that the lane becomes the row: a channel's store is then a run along n
+    float* region = s_all + wave * 32 * GX_P;
+    __syncthreads();                                           // the slabs this region overlays have been read by every wave
+#pragma unroll
+    for (int r = 0; r < 16; ++r) region[ghr_acc_row(r, half) * GX_P + col] = acc[0][r];
+    __syncthreads();
+    const int t = row0 + 32 * wr + col;
+    if (t < a.T) {
+      const int b = t / N, n = t - b * N;
+#pragma unroll
+      for (int it = 0; it < 16; ++it) {
+        const int ch = 2 * it + half, jj = c0 + 32 * wc + ch;
+        if (jj < a.N_out) {
+          float v = region[col * GX_P + ch];
+          if (a.res) v = v + a.res[(long long)b * a.res_stride_b + (long long)jj * a.res_stride + n];
+          a.y[(long long)b * a.y_stride_b + (long long)jj * a.y_stride + n] = v;
+        }
+      }
+    }
+  } else {
+    if (j < a.N_out) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const long long t = row0 + 32 * wr + ghr_acc_row(r, half);
+        if (t < a.T) {
+          float v = acc[0][r];
+          if constexpr (EPI == GH_XF_EPI_BIAS_RES) {
+            if (a.res) v = v + a.res[t * a.res_stride + j];
+          }
+          if constexpr (EPI == GH_XF_EPI_GEGLU) {
+            const float g = acc[NB - 1][r];
+            v = v * ((0.5f * g) * (1.0f + erff(g * 0.70710678118654752440f)));
+          }
+          a.y[t * a.y_stride + j] = v;
+        }
+      }
+    }
+  }
+}
+
+// ---- attention -------------------------------------------------------------------------------------------------------------------------
+template <int ND>
+__global__ __launch_bounds__(GHR_BLOCK) void gx_attn_kernel(const float* __restrict__ qkv, long long stride, float* __restrict__ out,
+                                                             long long out_stride, int N, int H, float scale, int vec, int nq_tiles) {
+  constexpr int D = 32 * ND, P = D + 1;
+  constexpr int SLOT = 16 * ND + 2;                            // floats a lane hands to its partner wave
+  __shared__ float s_stage[2 * GH_XF_ATTN_KEYS * P];
+  static_assert(2 * GH_XF_ATTN_KEYS * P >= 2 * 64 * SLOT && 2 * GH_XF_ATTN_KEYS * P >= 2 * 32 * P, "the stage doubles as the join and the transpose");
+  float* s_k = s_stage;
+  float* s_v = s_stage + GH_XF_ATTN_KEYS * P;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int qi = wave >> 1, kh = wave & 1;
+  const int qt = blockIdx.x % nq_tiles, bh = blockIdx.x / nq_tiles, b = bh / H, h = bh - b * H;
+  const int M = H * D;
+  const float* q = qkv + (long long)b * N * stride + h * D;
+  const float* k = q + M;
+  const float* v = q + 2 * M;
+  const int row0 = qt * GH_XF_ATTN_ROWS + qi * 32, row = row0 + col;
+
+  float qr[16 * ND];
+#pragma unroll
+  for (int s = 0; s < 16 * ND; ++s) qr[s] = row < N ? q[(long long)row * stride + 2 * s + half] : 0.f;
+  ghr_acc o[ND];
+#pragma unroll
+  for (int t = 0; t < ND; ++t) o[t] = gx_splat(0.f);
+  float m = -INFINITY, l = 0.f;
+
+  const int sub = 32 * kh;
+  GhrSlab<2 * ND, 8 * ND> ks, vs;                              // 64 keys x D columns each; rows past N arrive as zeros
+  ghr_fetch_in(ks, k, stride, 0, 0, N, D, vec, tid);
+  ghr_fetch_in(vs, v, stride, 0, 0, N, D, vec, tid);
+  for (int kt = 0; kt < N; kt += GH_XF_ATTN_KEYS) {
+    __syncthreads();                                           // the previous stage has been read by every wave
+    ghr_put(ks, s_k, P, tid);
+    ghr_put(vs, s_v, P, tid);
+    __syncthreads();
+    if (kt + GH_XF_ATTN_KEYS < N) {                            // the next stage's loads fly under this stage's products
+      ghr_fetch_in(ks, k, stride, kt + GH_XF_ATTN_KEYS, 0, N, D, vec, tid);
+      ghr_fetch_in(vs, v, stride, kt + GH_XF_ATTN_KEYS, 0, N, D, vec, tid);
+    }
+    if (kt + sub < N) {                                        // wave-uniform: the tile holds at least one key
+      ghr_acc st = gx_splat(0.f);
+      const float* ap = s_k + (sub + col) * P + half;
+#pragma unroll
+      for (int s = 0; s < 16 * ND; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], qr[s], st, 0, 0, 0);
+      float p[16];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[r] = kt + sub + ghr_acc_row(r, half) < N ? st[r] * scale : -INFINITY;
+        mx = fmaxf(mx, p[r]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float m_new = fmaxf(m, mx);
+      const float alpha = expf(m - m_new);
+      float sum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[r] = expf(p[r] - m_new);
+        sum += p[r];
+      }
+      sum += __shfl_xor(sum, 32);
+      l = l * alpha + sum;
+      m = m_new;
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_v[(sub + ghr_acc_row(r, half)) * P + 32 * t + col], p[r], o[t], 0, 0, 0);
+      }
+    }
+  }
+
+  // the pair's join: the odd wave hands over through LDS, element e of lane l at [e * 64 + l]
+  float* join = s_stage + qi * 64 * SLOT;
+  __syncthreads();                                             // the last stage has been read by every wave
+  if (kh == 1) {
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) join[(16 * t + r) * 64 + lane] = o[t][r];
+    }
+    join[(16 * ND) * 64 + lane] = m;
+    join[(16 * ND + 1) * 64 + lane] = l;
+  }
+  __syncthreads();
+  if (kh == 0) {
+    const float m1 = join[(16 * ND) * 64 + lane], l1 = join[(16 * ND + 1) * 64 + lane];
+    const float mm = fmaxf(m, m1);                             // finite: the even wave met key 0
+    const float a0 = expf(m - mm), a1 = expf(m1 - mm);
+    l = l * a0 + l1 * a1;
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[t][r] = (o[t][r] * a0 + join[(16 * t + r) * 64 + lane] * a1) / l;
+    }
+  }
+  __syncthreads();                                             // the join has been read: the transpose overlays it
+  float* region = s_stage + qi * 32 * P;                       // [query][d]
+  if (kh == 0) {
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) region[col * P + 32 * t + ghr_acc_row(r, half)] = o[t][r];
+    }
+  }
+  __syncthreads();
+  // both waves of the pair store: wave kh the queries 16 kh .. 16 kh + 15, a half wave one run of 32 floats
+  float* dst = out + (long long)b * N * out_stride + h * D;
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int rq = 16 * kh + 2 * it + half;
+    if (row0 + rq < N) {
+#pragma unroll
+      for (int t = 0; t < ND; ++t) dst[(long long)(row0 + rq) * out_stride + 32 * t + col] = region[rq * P + 32 * t + col];
+    }
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------------
+static bool gx_launched() { return hipGetLastError() == hipSuccess; }
+
+static int gx_tiles(long long a, long long b, int* out) {      // a * b workgroups within int32
+  if (a * b > INT_MAX) return GH_ERR_UNSUPPORTED;
+  *out = (int)(a * b);
+  return GH_OK;
+}
+
+static int gx_check_linear(const GhXfLinear* a, bool* empty) {
+  *empty = true;
+  if (!a || a->T < 0 || a->K < 1 || a->N_out < 1) return GH_ERR_INVALID_ARG;
+  if (a->prologue < GH_XF_PRO_NONE || a->prologue > GH_XF_PRO_GN || a->epilogue < GH_XF_EPI_PLAIN || a->epilogue > GH_XF_EPI_BIAS_RES_CF)
+    return GH_ERR_INVALID_ARG;
+  if (a->K % 32 != 0 || a->K > GH_XF_MAX_K || a->T > GH_XF_MAX_T || a->N_out > GH_XF_MAX_N_OUT) return GH_ERR_UNSUPPORTED;
+  const bool batched = a->prologue == GH_XF_PRO_GN || a->epilogue == GH_XF_EPI_BIAS_RES_CF;
+  if (batched && a->T > 0 && (a->rows_per_batch < 1 || a->T % a->rows_per_batch != 0)) return GH_ERR_INVALID_ARG;
+  if (a->prologue == GH_XF_PRO_GN && (a->groups < 1 || a->K % a->groups != 0)) return GH_ERR_INVALID_ARG;
+  if (a->prologue != GH_XF_PRO_NONE && !(a->eps >= 0.f && isfinite(a->eps))) return GH_ERR_INVALID_ARG;
+  *empty = a->T == 0;
+  if (*empty) return GH_OK;
+  if (!a->x || !a->w || !a->y || !ghr_al4(a->x) || !ghr_al4(a->w) || !ghr_al4(a->y) || !ghr_al4(a->bias) || !ghr_al4(a->res)) return GH_ERR_INVALID_ARG;
+  if (a->prologue != GH_XF_PRO_NONE && (!a->gamma || !a->beta || !ghr_al4(a->gamma) || !ghr_al4(a->beta))) return GH_ERR_INVALID_ARG;
+  if (a->prologue == GH_XF_PRO_GN && (!a->moments || !ghr_al4(a->moments))) return GH_ERR_INVALID_ARG;
+  if (a->prologue != GH_XF_PRO_GN && a->x_stride < a->K) return GH_ERR_INVALID_ARG;
+  if (a->epilogue != GH_XF_EPI_PLAIN && !a->bias) return GH_ERR_INVALID_ARG;
+  if (a->epilogue != GH_XF_EPI_BIAS_RES_CF && a->y_stride < a->N_out) return GH_ERR_INVALID_ARG;
+  return GH_OK;
+}
+
+extern "C" size_t gh_xf_linear_workspace_bytes(int T, int prologue) {
+  if (T <= 0 || T > GH_XF_MAX_T || prologue != GH_XF_PRO_LN) return 0;
+  return ghr_align((size_t)T * 2 * sizeof(float));
+}
+
+template <int PRO>
+static void gx_launch_linear(const GhXfLinear& a, const float* ln_mom, int vec_x, int vec_w, int ncol, int grid, hipStream_t s) {
+  const dim3 g((unsigned)grid), blk(GHR_BLOCK);
+  switch (a.epilogue) {
+    case GH_XF_EPI_PLAIN: hipLaunchKernelGGL((gx_linear_kernel<PRO, GH_XF_EPI_PLAIN>), g, blk, 0, s, a, ln_mom, vec_x, vec_w, ncol); break;
+    case GH_XF_EPI_BIAS_RES: hipLaunchKernelGGL((gx_linear_kernel<PRO, GH_XF_EPI_BIAS_RES>), g, blk, 0, s, a, ln_mom, vec_x, vec_w, ncol); break;
+    case GH_XF_EPI_GEGLU: hipLaunchKernelGGL((gx_linear_kernel<PRO, GH_XF_EPI_GEGLU>), g, blk, 0, s, a, ln_mom, vec_x, vec_w, ncol); break;
+    default: hipLaunchKernelGGL((gx_linear_kernel<PRO, GH_XF_EPI_BIAS_RES_CF>), g, blk, 0, s, a, ln_mom, vec_x, vec_w, ncol); break;
+  }
+}
+
+extern "C" int gh_xf_linear(const GhXfLinear* a, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_linear(a, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  const int ncol = (a->N_out + GX_TC - 1) / GX_TC, nrow = (a->T + GX_TR - 1) / GX_TR;
+  int grid;
+  if (gx_tiles(ncol, nrow, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;
+  float* ln_mom = nullptr;
+  if (a->prologue == GH_XF_PRO_LN) {
+    if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+    if (ws_bytes < gh_xf_linear_workspace_bytes(a->T, a->prologue)) return GH_ERR_WORKSPACE_SMALL;
+    ln_mom = (float*)workspace;
+  }
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  if (ln_mom) {
+    hipLaunchKernelGGL(gx_row_moments_kernel, dim3((unsigned)((a->T + GX_LN_ROWS - 1) / GX_LN_ROWS)), dim3(GHR_BLOCK), 0, s, a->x,
+                       (long long)a->x_stride, a->T, a->K, a->eps, ln_mom);
+    if (!gx_launched()) return GH_ERR_LAUNCH;
+  }
+  const int vec_x = a->prologue != GH_XF_PRO_GN && ghr_al16(a->x) && a->x_stride % 4 == 0, vec_w = ghr_al16(a->w);
+  switch (a->prologue) {
+    case GH_XF_PRO_NONE: gx_launch_linear<GH_XF_PRO_NONE>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
+    case GH_XF_PRO_LN: gx_launch_linear<GH_XF_PRO_LN>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
+    default: gx_launch_linear<GH_XF_PRO_GN>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
+  }
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+static int gx_check_groups(int B, int C, int N, int G, bool* empty) {
+  *empty = true;
+  if (B < 0 || N < 0 || C < 1 || G < 1 || C % G != 0) return GH_ERR_INVALID_ARG;
+  if (C > GH_XF_MAX_C || (long long)B * N > GH_XF_MAX_T) return GH_ERR_UNSUPPORTED;
+  *empty = B == 0 || N == 0;
+  if (*empty) return GH_OK;
+  int grid;
+  return gx_tiles((long long)B * G, (N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, &grid);
+}
+
+extern "C" size_t gh_xf_group_moments_workspace_bytes(int B, int C, int N, int G) {
+  bool empty;
+  if (gx_check_groups(B, C, N, G, &empty) != GH_OK || empty) return 0;
+  return ghr_align((size_t)B * G * ((N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK) * 2 * sizeof(float));
+}
+
+extern "C" int gh_xf_group_moments(const float* x, int64_t stride_b, int64_t stride_c, int B, int C, int N, int G, float* moments,
+                                   void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_groups(B, C, N, G, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  if (!x || !moments || !ghr_al4(x) || !ghr_al4(moments) || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (ws_bytes < gh_xf_group_moments_workspace_bytes(B, C, N, G)) return GH_ERR_WORKSPACE_SMALL;
+  const int nchunks = (N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, BG = B * G;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_group_part_kernel, dim3((unsigned)(BG * nchunks)), dim3(GHR_BLOCK), 0, s, x, (long long)stride_b, (long long)stride_c, N,
+                     G, C / G, nchunks, (float*)workspace);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  hipLaunchKernelGGL(gx_group_join_kernel, dim3((unsigned)((BG + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, (const float*)workspace,
+                     BG, N, C / G, nchunks, moments);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+static int gx_check_attn(int B, int N, int heads, int D, int* grid, bool* empty) {
+  *empty = true;
+  if (B < 0 || N < 0 || heads < 1 || D < 1) return GH_ERR_INVALID_ARG;
+  if ((D != 32 && D != 64) || (long long)heads * D > GH_XF_MAX_M || (long long)B * N > GH_XF_MAX_T) return GH_ERR_UNSUPPORTED;
+  *empty = B == 0 || N == 0;
+  if (*empty) return GH_OK;
+  return gx_tiles((long long)B * heads, (N + GH_XF_ATTN_ROWS - 1) / GH_XF_ATTN_ROWS, grid);
+}
+
+extern "C" int gh_xf_attention(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride,
+                               void* hip_stream) {
+  bool empty;
+  int grid = 0;
+  const int rc = gx_check_attn(B, N, heads, D, &grid, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  const int M = heads * D;
+  if (!qkv || !out || !ghr_al4(qkv) || !ghr_al4(out) || qkv_stride < 3 * M || out_stride < M) return GH_ERR_INVALID_ARG;
+  const int vec = ghr_al16(qkv) && qkv_stride % 4 == 0, nq = (N + GH_XF_ATTN_ROWS - 1) / GH_XF_ATTN_ROWS;
+  const float scale = (float)(1.0 / sqrt((double)D));
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  if (D == 32) {
+    hipLaunchKernelGGL(gx_attn_kernel<1>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out, (long long)out_stride, N,
+                       heads, scale, vec, nq);
+  } else {
+    hipLaunchKernelGGL(gx_attn_kernel<2>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out, (long long)out_stride, N,
+                       heads, scale, vec, nq);
+  }
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+// the workspace of a whole forward: h (T, M), qkv (T, 3M), att (T, M), ff (T, 4M), the LayerNorm's row moments, the GroupNorm's
+// moments and their partials
+struct GxPlan {
+  size_t h, qkv, att, ff, ln, gn, gnp, total;
+};
+
+static int gx_check_dims(const GhXfDims* d, bool* empty) {
+  *empty = true;
+  if (!d || d->B < 0 || d->N < 0 || d->C < 1 || d->G < 1 || d->heads < 1 || d->D < 1 || d->layers < 0 || d->C % d->G != 0) return GH_ERR_INVALID_ARG;
+  if (!(d->gn_eps >= 0.f && isfinite(d->gn_eps)) || !(d->ln_eps >= 0.f && isfinite(d->ln_eps))) return GH_ERR_INVALID_ARG;
+  if ((d->D != 32 && d->D != 64) || (long long)d->heads * d->D > GH_XF_MAX_M || d->C > GH_XF_MAX_C || d->C % 32 != 0) return GH_ERR_UNSUPPORTED;
+  if ((long long)d->B * d->N > GH_XF_MAX_T) return GH_ERR_UNSUPPORTED;
+  *empty = d->B == 0 || d->N == 0;
+  if (*empty) return GH_OK;
+  const long long T = (long long)d->B * d->N, rows = (T + GX_TR - 1) / GX_TR, M = (long long)d->heads * d->D;
+  int grid;
+  if (gx_tiles(rows, (4 * M + GX_TC - 1) / GX_TC, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;   // the widest product
+  if (gx_tiles((long long)d->B * d->heads, (d->N + GH_XF_ATTN_ROWS - 1) / GH_XF_ATTN_ROWS, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;
+  return gx_tiles((long long)d->B * d->G, (d->N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, &grid);
+}
+
+static GxPlan gx_plan(const GhXfDims* d) {
+  const size_t T = (size_t)d->B * d->N, M = (size_t)d->heads * d->D, f = sizeof(float);
+  GxPlan p;
+  size_t at = 0;
+  p.h = at; at += ghr_align(T * M * f);
+  p.qkv = at; at += ghr_align(T * 3 * M * f);
+  p.att = at; at += ghr_align(T * M * f);
+  p.ff = at; at += ghr_align(T * 4 * M * f);
+  p.ln = at; at += gh_xf_linear_workspace_bytes((int)T, GH_XF_PRO_LN);
+  p.gn = at; at += ghr_align((size_t)d->B * d->G * 2 * f);
+  p.gnp = at; at += gh_xf_group_moments_workspace_bytes(d->B, d->C, d->N, d->G);
+  p.total = at;
+  return p;
+}
+
+extern "C" size_t gh_xf_workspace_bytes(const GhXfDims* dims) {
+  bool empty;
+  if (gx_check_dims(dims, &empty) != GH_OK || empty) return 0;
+  return gx_plan(dims).total;
+}
+
+extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out, void* workspace,
+                             size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  int rc = gx_check_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  if (!stem || (d->layers > 0 && !layers) || !x || !out || x == out || !ghr_al4(x) || !ghr_al4(out)) return GH_ERR_INVALID_ARG;
+  const float* sp[] = {stem->gn_w, stem->gn_b, stem->in_w, stem->in_b, stem->out_w, stem->out_b};
+  for (const float* p : sp) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < d->layers; ++i) {
+    const GhXfLayer& L = layers[i];
+    const float* need[] = {L.ln1_w, L.ln1_b, L.qkv1, L.o1_w, L.o1_b, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, L.ff2_w, L.ff2_b};
+    for (const float* p : need) {
+      if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+    }
+    if (L.qkv2) {
+      const float* second[] = {L.qkv2, L.ln2_w, L.ln2_b, L.o2_w, L.o2_b};
+      for (const float* p : second) {
+        if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+      }
+    }
+  }
+  if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  const GxPlan p = gx_plan(d);
+  if (ws_bytes < p.total) return GH_ERR_WORKSPACE_SMALL;
+
+  char* ws = (char*)workspace;
+  float* h = (float*)(ws + p.h);
+  float* qkv = (float*)(ws + p.qkv);
+  float* att = (float*)(ws + p.att);
+  float* ff = (float*)(ws + p.ff);
+  float* gn = (float*)(ws + p.gn);
+  void* ln = ws + p.ln;
+  const size_t ln_bytes = p.gn - p.ln;
+  const int T = d->B * d->N, M = d->heads * d->D, C = d->C, N = d->N;
+
+  rc = gh_xf_group_moments(x, (int64_t)C * N, N, d->B, C, N, d->G, gn, ws + p.gnp, p.total - p.gnp, hip_stream);
+  if (rc != GH_OK) return rc;
+
+  GhXfLinear a = {};
+  a.T = T; a.K = C; a.N_out = M; a.prologue = GH_XF_PRO_GN; a.epilogue = GH_XF_EPI_BIAS_RES; a.rows_per_batch = N; a.groups = d->G;
+  a.eps = d->gn_eps; a.x = x; a.x_stride = N; a.x_stride_b = (int64_t)C * N; a.w = stem->in_w; a.bias = stem->in_b; a.gamma = stem->gn_w;
+  a.beta = stem->gn_b; a.moments = gn; a.y = h; a.y_stride = M;
+  rc = gh_xf_linear(&a, nullptr, 0, hip_stream);
+  if (rc != GH_OK) return rc;
+
+  // y = epilogue(LN(h) w^T) or epilogue(src w^T)
+  auto product = [&](int pro, int epi, const float* src, int K, const float* gamma, const float* beta, const float* w, const float* bias,
+                     int n_out, const float* res, float* y) {
+    GhXfLinear l = {};
+    l.T = T; l.K = K; l.N_out = n_out; l.prologue = pro; l.epilogue = epi; l.eps = d->ln_eps; l.x = src; l.x_stride = K; l.w = w; l.bias = bias;
+    l.gamma = gamma; l.beta = beta; l.res = res; l.res_stride = n_out; l.y = y; l.y_stride = n_out;
+    return gh_xf_linear(&l, ln, ln_bytes, hip_stream);
+  };
+  for (int i = 0; i < d->layers; ++i) {
+    const GhXfLayer& L = layers[i];
+    for (int which = 0; which < 2; ++which) {
+      const float* wqkv = which ? L.qkv2 : L.qkv1;
+      if (!wqkv) continue;
+      rc = product(GH_XF_PRO_LN, GH_XF_EPI_PLAIN, h, M, which ? L.ln2_w : L.ln1_w, which ? L.ln2_b : L.ln1_b, wqkv, nullptr, 3 * M, nullptr, qkv);
+      if (rc != GH_OK) return rc;
+      rc = gh_xf_attention(qkv, 3 * M, d->B, N, d->heads, d->D, att, M, hip_stream);
+      if (rc != GH_OK) return rc;
+      rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, att, M, nullptr, nullptr, which ? L.o2_w : L.o1_w, which ? L.o2_b : L.o1_b, M, h, h);
+      if (rc != GH_OK) return rc;
+    }
+    rc = product(GH_XF_PRO_LN, GH_XF_EPI_GEGLU, h, M, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, 4 * M, nullptr, ff);
+    if (rc != GH_OK) return rc;
+    rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, ff, 4 * M, nullptr, nullptr, L.ff2_w, L.ff2_b, M, h, h);
+    if (rc != GH_OK) return rc;
+  }
+
+  GhXfLinear z = {};
+  z.T = T; z.K = M; z.N_out = C; z.prologue = GH_XF_PRO_NONE; z.epilogue = GH_XF_EPI_BIAS_RES_CF; z.rows_per_batch = N; z.x = h; z.x_stride = M;
+  z.w = stem->out_w; z.bias = stem->out_b; z.res = x; z.res_stride = N; z.res_stride_b = (int64_t)C * N; z.y = out; z.y_stride = N;
+  z.y_stride_b = (int64_t)C * N;
+  return gh_xf_linear(&z, nullptr, 0, hip_stream);
+}
