@@ -568,7 +568,7 @@ def declare_mano(lib: C.CDLL) -> None:
     lib.gh_mano_backward.argtypes = [D, M, V, V, C.POINTER(GhManoGrads), V, C.c_size_t, V]
 
 
-# ---- include/gh_xf.h: the Transformer1D backbones' forward (a header of its own, as gh_mano.h is) ----
+# ---- include/gh_xf.h: the Transformer1D backbones' forward and backward to the input (a header of its own, as gh_mano.h is) ----
 GH_XF_ROWS = 64
 GH_XF_COLS = 64
 GH_XF_ATTN_ROWS = 64
@@ -579,12 +579,19 @@ GH_XF_MAX_C = 1024
 GH_XF_MAX_K = 4096
 GH_XF_MAX_N_OUT = 8192
 GH_XF_MAX_T = 1 << 30
-GH_XF_PRO_NONE, GH_XF_PRO_LN, GH_XF_PRO_GN = 0, 1, 2
+GH_XF_ATTN_BWD_ROWS = 128
+GH_XF_ATTN_BWD_STAGE = 64
+GH_XF_GRAD_MAX_M = 512
+GH_XF_PRO_NONE, GH_XF_PRO_LN, GH_XF_PRO_GN, GH_XF_PRO_CF = 0, 1, 2, 3
 GH_XF_EPI_PLAIN, GH_XF_EPI_BIAS_RES, GH_XF_EPI_GEGLU, GH_XF_EPI_BIAS_RES_CF = 0, 1, 2, 3
 
 XF_SYMBOLS = ("gh_xf_linear_workspace_bytes", "gh_xf_linear", "gh_xf_group_moments_workspace_bytes", "gh_xf_group_moments", "gh_xf_attention",
-              "gh_xf_workspace_bytes", "gh_xf_forward")
+              "gh_xf_workspace_bytes", "gh_xf_forward", "gh_xf_attention_lse", "gh_xf_attention_backward_workspace_bytes",
+              "gh_xf_attention_backward", "gh_xf_geglu_backward", "gh_xf_layernorm_backward", "gh_xf_group_norm_backward_workspace_bytes",
+              "gh_xf_group_norm_backward", "gh_xf_tape_bytes", "gh_xf_forward_tape", "gh_xf_backward_workspace_bytes", "gh_xf_backward")
 XF_STEM = ("gn_w", "gn_b", "in_w", "in_b", "out_w", "out_b")
+XF_STEM_T = ("gn_w", "in_t", "out_t")
+XF_LAYER_T = ("ln1_w", "qkv1_t", "o1_t", "ln2_w", "qkv2_t", "o2_t", "ln3_w", "ln3_b", "ff1_w", "ff1_b", "ff1_t", "ff2_t")
 XF_LAYER = ("ln1_w", "ln1_b", "qkv1", "o1_w", "o1_b", "ln2_w", "ln2_b", "qkv2", "o2_w", "o2_b", "ln3_w", "ln3_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b")
 
 
@@ -609,6 +616,14 @@ class GhXfLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in XF_LAYER]
 
 
+class GhXfStemT(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in XF_STEM_T]
+
+
+class GhXfLayerT(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in XF_LAYER_T]
+
+
 def declare_xf(lib: C.CDLL) -> None:
     """Attach argtypes/restypes for every symbol include/gh_xf.h declares."""
     V, I, L = C.c_void_p, C.c_int, C.c_int64
@@ -626,6 +641,28 @@ def declare_xf(lib: C.CDLL) -> None:
     lib.gh_xf_workspace_bytes.argtypes = [C.POINTER(GhXfDims)]
     lib.gh_xf_forward.restype = C.c_int
     lib.gh_xf_forward.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStem), C.POINTER(GhXfLayer), V, V, V, C.c_size_t, V]
+    lib.gh_xf_attention_lse.restype = C.c_int
+    lib.gh_xf_attention_lse.argtypes = [V, L, I, I, I, I, V, L, V, V]
+    lib.gh_xf_attention_backward_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_attention_backward_workspace_bytes.argtypes = [I, I, I]
+    lib.gh_xf_attention_backward.restype = C.c_int
+    lib.gh_xf_attention_backward.argtypes = [V, L, V, L, V, V, L, I, I, I, I, V, L, V, C.c_size_t, V]
+    lib.gh_xf_geglu_backward.restype = C.c_int
+    lib.gh_xf_geglu_backward.argtypes = [V, L, V, L, V, V, V, V, V, V, I, I, V, L, V]
+    lib.gh_xf_layernorm_backward.restype = C.c_int
+    lib.gh_xf_layernorm_backward.argtypes = [V, L, V, L, V, V, I, I, V, L, V]
+    lib.gh_xf_group_norm_backward_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_group_norm_backward_workspace_bytes.argtypes = [I, I, I, I]
+    lib.gh_xf_group_norm_backward.restype = C.c_int
+    lib.gh_xf_group_norm_backward.argtypes = [V, V, V, V, V, V, I, I, I, I, C.c_float, V, C.c_size_t, V]
+    lib.gh_xf_tape_bytes.restype = C.c_size_t
+    lib.gh_xf_tape_bytes.argtypes = [C.POINTER(GhXfDims)]
+    lib.gh_xf_forward_tape.restype = C.c_int
+    lib.gh_xf_forward_tape.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStem), C.POINTER(GhXfLayer), V, V, V, C.c_size_t, V, C.c_size_t, V]
+    lib.gh_xf_backward_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_backward_workspace_bytes.argtypes = [C.POINTER(GhXfDims)]
+    lib.gh_xf_backward.restype = C.c_int
+    lib.gh_xf_backward.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStemT), C.POINTER(GhXfLayerT), V, V, V, V, V, C.c_size_t, V]
 
 
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +

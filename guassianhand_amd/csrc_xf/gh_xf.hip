@@ -1,6 +1,8 @@
 // gh_xf.hip — the Transformer1D backbones' forward (include/gh_xf.h): the LDS-tiled product with its prologues and epilogues, the
 // LayerNorm and GroupNorm moments, the streaming-softmax attention for D = 32 and 64, and the host loop that enqueues a whole
-// backbone. Exact float32 MFMA, no atomics, no workgroup that waits for another.
+// backbone; behind them the backward to the input for frozen weights (the taped forward is the same host loop with other pointers;
+// the attention's, the GEGLU's and the norms' backward kernels, the host loop in reverse). Exact float32 MFMA, no atomics, no workgroup
+// that waits for another.
 //
 // The product shape is gh_rows.h's "columns" turned round: v_mfma_f32_32x32x2_f32 with the ROW of X as the A operand's i and the
 // output channel as the B operand's j, so that lane l holds channel j = l & 31 of the rows ghr_acc_row(r, l >> 5) and a register's
@@ -118,7 +120,10 @@ __global__ __launch_bounds__(GHR_BLOCK) void gx_group_join_kernel(const float* _
 // ---- the product ---------------------------------------------------------------------------------------------------------------------
 // One slab of X on its way into LDS. PRO_NONE and PRO_LN: gh_rows.h's window, element (r, c) = X[row0 + r][k0 + c], thread i moves
 // rows i / 8 and (i + 256) / 8. PRO_GN: X is channel first, so consecutive threads take consecutive rows: thread i owns tile row
-// i & 63 and the wave-uniform columns (i >> 6) + 4 it.
+// i & 63 and the wave-uniform columns (i >> 6) + 4 it. PRO_CF: the same read, no norm.
+template <int PRO>
+constexpr bool gx_cf = PRO == GH_XF_PRO_GN || PRO == GH_XF_PRO_CF;
+
 template <int PRO>
 struct GxSlabX {
   GhrSlab<2, 8> w;
@@ -128,7 +133,7 @@ struct GxSlabX {
 template <int PRO>
 __device__ __forceinline__ void gx_fetch_x(GxSlabX<PRO>& t, const GhXfLinear& a, int row0, int k0, int vec, long long gn_base, bool gn_live,
                                            int tid) {
-  if constexpr (PRO == GH_XF_PRO_GN) {
+  if constexpr (gx_cf<PRO>) {
 #pragma unroll
     for (int it = 0; it < 8; ++it) t.g[it] = gn_live ? a.x[gn_base + (long long)(k0 + (tid >> 6) + 4 * it) * a.x_stride] : 0.f;
   } else {
@@ -141,7 +146,10 @@ __device__ __forceinline__ void gx_fetch_x(GxSlabX<PRO>& t, const GhXfLinear& a,
 template <int PRO>
 __device__ __forceinline__ void gx_put_x(const GxSlabX<PRO>& t, float* s_x, const GhXfLinear& a, int k0, const float (&ln)[2][2],
                                          const float* __restrict__ gn_mom, int cpg, float gn_cnt, int tid) {
-  if constexpr (PRO == GH_XF_PRO_GN) {
+  if constexpr (PRO == GH_XF_PRO_CF) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) s_x[(tid & 63) * GX_P + (tid >> 6) + 4 * it] = t.g[it];
+  } else if constexpr (PRO == GH_XF_PRO_GN) {
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int kk = (tid >> 6) + 4 * it, c = k0 + kk, g = c / cpg;
@@ -193,14 +201,16 @@ __global__ __launch_bounds__(GHR_BLOCK) void gx_linear_kernel(GhXfLinear a, cons
   const float* gn_mom = nullptr;
   int cpg = 1;
   float gn_cnt = 1.f;
-  if constexpr (PRO == GH_XF_PRO_GN) {
+  if constexpr (gx_cf<PRO>) {
     const int t = row0 + (tid & 63);
     gn_live = t < a.T;
     const int b = gn_live ? t / N : 0, n = gn_live ? t - b * N : 0;
     gn_base = (long long)b * a.x_stride_b + n;
-    cpg = a.K / a.groups;
-    gn_cnt = (float)cpg * (float)N;
-    gn_mom = gn_live ? a.moments + 2 * (long long)b * a.groups : nullptr;
+    if constexpr (PRO == GH_XF_PRO_GN) {
+      cpg = a.K / a.groups;
+      gn_cnt = (float)cpg * (float)N;
+      gn_mom = gn_live ? a.moments + 2 * (long long)b * a.groups : nullptr;
+    }
   }
 
   const int j = c0 + 32 * wc + col;                            // the lane's output channel
@@ -280,9 +290,10 @@ __global__ __launch_bounds__(GHR_BLOCK) void gx_linear_kernel(GhXfLinear a, cons
 }
 
 // ---- attention -------------------------------------------------------------------------------------------------------------------------
-template <int ND>
+template <int ND, bool LSE>
 __global__ __launch_bounds__(GHR_BLOCK) void gx_attn_kernel(const float* __restrict__ qkv, long long stride, float* __restrict__ out,
-                                                             long long out_stride, int N, int H, float scale, int vec, int nq_tiles) {
+                                                             long long out_stride, int N, int H, float scale, int vec, int nq_tiles,
+                                                             float* __restrict__ lse) {
   constexpr int D = 32 * ND, P = D + 1;
   constexpr int SLOT = 16 * ND + 2;                            // floats a lane hands to its partner wave
   __shared__ float s_stage[2 * GH_XF_ATTN_KEYS * P];
@@ -372,6 +383,9 @@ __global__ __launch_bounds__(GHR_BLOCK) void gx_attn_kernel(const float* __restr
     const float mm = fmaxf(m, m1);                             // finite: the even wave met key 0
     const float a0 = expf(m - mm), a1 = expf(m1 - mm);
     l = l * a0 + l1 * a1;
+    if constexpr (LSE) {                                       // both halves of a lane pair hold the query's mm and l
+      if (half == 0 && row < N) lse[(long long)bh * N + row] = mm + logf(l);
+    }
 #pragma unroll
     for (int t = 0; t < ND; ++t) {
 #pragma unroll
@@ -409,23 +423,27 @@ static int gx_tiles(long long a, long long b, int* out) {      // a * b workgrou
   return GH_OK;
 }
 
-static int gx_check_linear(const GhXfLinear* a, bool* empty) {
+// need_bias: the C-ABI's rule that a biased epilogue has a bias; the backward's proj_in product runs BIAS_RES_CF with neither bias nor
+// residual (the chain then starts from zero, as under PLAIN)
+static int gx_check_linear(const GhXfLinear* a, bool* empty, bool need_bias) {
   *empty = true;
   if (!a || a->T < 0 || a->K < 1 || a->N_out < 1) return GH_ERR_INVALID_ARG;
-  if (a->prologue < GH_XF_PRO_NONE || a->prologue > GH_XF_PRO_GN || a->epilogue < GH_XF_EPI_PLAIN || a->epilogue > GH_XF_EPI_BIAS_RES_CF)
+  if (a->prologue < GH_XF_PRO_NONE || a->prologue > GH_XF_PRO_CF || a->epilogue < GH_XF_EPI_PLAIN || a->epilogue > GH_XF_EPI_BIAS_RES_CF)
     return GH_ERR_INVALID_ARG;
   if (a->K % 32 != 0 || a->K > GH_XF_MAX_K || a->T > GH_XF_MAX_T || a->N_out > GH_XF_MAX_N_OUT) return GH_ERR_UNSUPPORTED;
-  const bool batched = a->prologue == GH_XF_PRO_GN || a->epilogue == GH_XF_EPI_BIAS_RES_CF;
+  const bool normed = a->prologue == GH_XF_PRO_LN || a->prologue == GH_XF_PRO_GN;
+  const bool cf = a->prologue == GH_XF_PRO_GN || a->prologue == GH_XF_PRO_CF;
+  const bool batched = cf || a->epilogue == GH_XF_EPI_BIAS_RES_CF;
   if (batched && a->T > 0 && (a->rows_per_batch < 1 || a->T % a->rows_per_batch != 0)) return GH_ERR_INVALID_ARG;
   if (a->prologue == GH_XF_PRO_GN && (a->groups < 1 || a->K % a->groups != 0)) return GH_ERR_INVALID_ARG;
-  if (a->prologue != GH_XF_PRO_NONE && !(a->eps >= 0.f && isfinite(a->eps))) return GH_ERR_INVALID_ARG;
+  if (normed && !(a->eps >= 0.f && isfinite(a->eps))) return GH_ERR_INVALID_ARG;
   *empty = a->T == 0;
   if (*empty) return GH_OK;
   if (!a->x || !a->w || !a->y || !ghr_al4(a->x) || !ghr_al4(a->w) || !ghr_al4(a->y) || !ghr_al4(a->bias) || !ghr_al4(a->res)) return GH_ERR_INVALID_ARG;
-  if (a->prologue != GH_XF_PRO_NONE && (!a->gamma || !a->beta || !ghr_al4(a->gamma) || !ghr_al4(a->beta))) return GH_ERR_INVALID_ARG;
+  if (normed && (!a->gamma || !a->beta || !ghr_al4(a->gamma) || !ghr_al4(a->beta))) return GH_ERR_INVALID_ARG;
   if (a->prologue == GH_XF_PRO_GN && (!a->moments || !ghr_al4(a->moments))) return GH_ERR_INVALID_ARG;
-  if (a->prologue != GH_XF_PRO_GN && a->x_stride < a->K) return GH_ERR_INVALID_ARG;
-  if (a->epilogue != GH_XF_EPI_PLAIN && !a->bias) return GH_ERR_INVALID_ARG;
+  if (!cf && a->x_stride < a->K) return GH_ERR_INVALID_ARG;
+  if (need_bias && a->epilogue != GH_XF_EPI_PLAIN && !a->bias) return GH_ERR_INVALID_ARG;
   if (a->epilogue != GH_XF_EPI_BIAS_RES_CF && a->y_stride < a->N_out) return GH_ERR_INVALID_ARG;
   return GH_OK;
 }
@@ -446,9 +464,9 @@ static void gx_launch_linear(const GhXfLinear& a, const float* ln_mom, int vec_x
   }
 }
 
-extern "C" int gh_xf_linear(const GhXfLinear* a, void* workspace, size_t ws_bytes, void* hip_stream) {
+static int gx_linear(const GhXfLinear* a, void* workspace, size_t ws_bytes, void* hip_stream, bool need_bias) {
   bool empty;
-  const int rc = gx_check_linear(a, &empty);
+  const int rc = gx_check_linear(a, &empty, need_bias);
   if (rc != GH_OK) return rc;
   if (empty) return GH_OK;
   const int ncol = (a->N_out + GX_TC - 1) / GX_TC, nrow = (a->T + GX_TR - 1) / GX_TR;
@@ -467,13 +485,18 @@ extern "C" int gh_xf_linear(const GhXfLinear* a, void* workspace, size_t ws_byte
                        (long long)a->x_stride, a->T, a->K, a->eps, ln_mom);
     if (!gx_launched()) return GH_ERR_LAUNCH;
   }
-  const int vec_x = a->prologue != GH_XF_PRO_GN && ghr_al16(a->x) && a->x_stride % 4 == 0, vec_w = ghr_al16(a->w);
+  const int vec_x = (a->prologue == GH_XF_PRO_NONE || a->prologue == GH_XF_PRO_LN) && ghr_al16(a->x) && a->x_stride % 4 == 0, vec_w = ghr_al16(a->w);
   switch (a->prologue) {
     case GH_XF_PRO_NONE: gx_launch_linear<GH_XF_PRO_NONE>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
     case GH_XF_PRO_LN: gx_launch_linear<GH_XF_PRO_LN>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
+    case GH_XF_PRO_CF: gx_launch_linear<GH_XF_PRO_CF>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
     default: gx_launch_linear<GH_XF_PRO_GN>(*a, ln_mom, vec_x, vec_w, ncol, grid, s); break;
   }
   return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+extern "C" int gh_xf_linear(const GhXfLinear* a, void* workspace, size_t ws_bytes, void* hip_stream) {
+  return gx_linear(a, workspace, ws_bytes, hip_stream, true);
 }
 
 static int gx_check_groups(int B, int C, int N, int G, bool* empty) {
@@ -520,8 +543,9 @@ static int gx_check_attn(int B, int N, int heads, int D, int* grid, bool* empty)
   return gx_tiles((long long)B * heads, (N + GH_XF_ATTN_ROWS - 1) / GH_XF_ATTN_ROWS, grid);
 }
 
-extern "C" int gh_xf_attention(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride,
-                               void* hip_stream) {
+template <bool LSE>
+static int gx_attention(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride, float* lse,
+                        void* hip_stream) {
   bool empty;
   int grid = 0;
   const int rc = gx_check_attn(B, N, heads, D, &grid, &empty);
@@ -529,18 +553,29 @@ extern "C" int gh_xf_attention(const float* qkv, int64_t qkv_stride, int B, int 
   if (empty) return GH_OK;
   const int M = heads * D;
   if (!qkv || !out || !ghr_al4(qkv) || !ghr_al4(out) || qkv_stride < 3 * M || out_stride < M) return GH_ERR_INVALID_ARG;
+  if (LSE && (!lse || !ghr_al4(lse))) return GH_ERR_INVALID_ARG;
   const int vec = ghr_al16(qkv) && qkv_stride % 4 == 0, nq = (N + GH_XF_ATTN_ROWS - 1) / GH_XF_ATTN_ROWS;
   const float scale = (float)(1.0 / sqrt((double)D));
   hipStream_t s = (hipStream_t)hip_stream;
   (void)hipGetLastError();
   if (D == 32) {
-    hipLaunchKernelGGL(gx_attn_kernel<1>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out, (long long)out_stride, N,
-                       heads, scale, vec, nq);
+    hipLaunchKernelGGL((gx_attn_kernel<1, LSE>), dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out,
+                       (long long)out_stride, N, heads, scale, vec, nq, lse);
   } else {
-    hipLaunchKernelGGL(gx_attn_kernel<2>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out, (long long)out_stride, N,
-                       heads, scale, vec, nq);
+    hipLaunchKernelGGL((gx_attn_kernel<2, LSE>), dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, out,
+                       (long long)out_stride, N, heads, scale, vec, nq, lse);
   }
   return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+extern "C" int gh_xf_attention(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride,
+                               void* hip_stream) {
+  return gx_attention<false>(qkv, qkv_stride, B, N, heads, D, out, out_stride, nullptr, hip_stream);
+}
+
+extern "C" int gh_xf_attention_lse(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride,
+                                   float* lse, void* hip_stream) {
+  return gx_attention<true>(qkv, qkv_stride, B, N, heads, D, out, out_stride, lse, hip_stream);
 }
 
 // the workspace of a whole forward: h (T, M), qkv (T, 3M), att (T, M), ff (T, 4M), the LayerNorm's row moments, the GroupNorm's
@@ -585,12 +620,51 @@ extern "C" size_t gh_xf_workspace_bytes(const GhXfDims* dims) {
   return gx_plan(dims).total;
 }
 
-extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out, void* workspace,
-                             size_t ws_bytes, void* hip_stream) {
-  bool empty;
-  int rc = gx_check_dims(d, &empty);
+// ---- the tape of gh_xf_forward_tape (include/gh_xf.h): byte offsets; a slot's parts are relative to the slot ----------------------------
+struct GxTape {
+  size_t gn, layer0, layer_stride, total;
+  size_t a_ln, a_qkv, a_att, a_lse, a_size;                    // an attention slot: h at 0
+  size_t f_ln, f_size;                                         // the feed-forward's slot: h at 0
+};
+
+static GxTape gx_tape(const GhXfDims* d) {
+  const size_t T = (size_t)d->B * d->N, M = (size_t)d->heads * d->D, f = sizeof(float);
+  GxTape t;
+  size_t at = ghr_align(T * M * f);
+  t.a_ln = at; at += ghr_align(T * 2 * f);
+  t.a_qkv = at; at += ghr_align(T * 3 * M * f);
+  t.a_att = at; at += ghr_align(T * M * f);
+  t.a_lse = at; at += ghr_align(T * d->heads * f);
+  t.a_size = at;
+  t.f_ln = ghr_align(T * M * f);
+  t.f_size = t.f_ln + ghr_align(T * 2 * f);
+  t.gn = 0;
+  t.layer0 = ghr_align((size_t)d->B * d->G * 2 * f);
+  t.layer_stride = 2 * t.a_size + t.f_size;
+  t.total = t.layer0 + (size_t)d->layers * t.layer_stride;
+  return t;
+}
+
+static char* gx_slot(const GxTape& t, char* tape, int layer, int which) {   // which: 0 attn1, 1 attn2, 2 the feed-forward
+  return tape + t.layer0 + (size_t)layer * t.layer_stride + (size_t)which * t.a_size;
+}
+
+static int gx_check_grad_dims(const GhXfDims* d, bool* empty) {
+  const int rc = gx_check_dims(d, empty);
   if (rc != GH_OK) return rc;
-  if (empty) return GH_OK;
+  if ((long long)d->heads * d->D > GH_XF_GRAD_MAX_M) { *empty = true; return GH_ERR_UNSUPPORTED; }
+  if (*empty) return GH_OK;
+  int grid;
+  const long long T = (long long)d->B * d->N, M = (long long)d->heads * d->D;
+  if (gx_tiles((T + GX_TR - 1) / GX_TR, (8 * M + GX_TC - 1) / GX_TC, &grid) != GH_OK) { *empty = true; return GH_ERR_UNSUPPORTED; }
+  if (gx_tiles((long long)d->B * d->C, (d->N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, &grid) != GH_OK) { *empty = true; return GH_ERR_UNSUPPORTED; }
+  return GH_OK;
+}
+
+// the forward's host loop. tape == nullptr: every intermediate lives in the workspace and the stream h is updated in place. Otherwise
+// what the backward reads goes to the tape: each sub-block reads h from its own slot and writes the next sub-block's.
+static int gx_forward(const GhXfDims* d, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out, char* tape,
+                      void* workspace, size_t ws_bytes, void* hip_stream) {
   if (!stem || (d->layers > 0 && !layers) || !x || !out || x == out || !ghr_al4(x) || !ghr_al4(out)) return GH_ERR_INVALID_ARG;
   const float* sp[] = {stem->gn_w, stem->gn_b, stem->in_w, stem->in_b, stem->out_w, stem->out_b};
   for (const float* p : sp) {
@@ -612,16 +686,24 @@ extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXf
   if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
   const GxPlan p = gx_plan(d);
   if (ws_bytes < p.total) return GH_ERR_WORKSPACE_SMALL;
+  const GxTape tp = gx_tape(d);
 
   char* ws = (char*)workspace;
   float* h = (float*)(ws + p.h);
-  float* qkv = (float*)(ws + p.qkv);
-  float* att = (float*)(ws + p.att);
   float* ff = (float*)(ws + p.ff);
-  float* gn = (float*)(ws + p.gn);
-  void* ln = ws + p.ln;
+  float* gn = tape ? (float*)(tape + tp.gn) : (float*)(ws + p.gn);
   const size_t ln_bytes = p.gn - p.ln;
   const int T = d->B * d->N, M = d->heads * d->D, C = d->C, N = d->N;
+  int rc;
+
+  // where the stream goes after sub-block `which` of layer i: the next sub-block's slot, the workspace behind the last
+  auto next = [&](int i, int which) -> float* {
+    if (!tape) return h;
+    if (which == 0 && layers[i].qkv2) return (float*)gx_slot(tp, tape, i, 1);
+    if (which < 2) return (float*)gx_slot(tp, tape, i, 2);
+    return i + 1 < d->layers ? (float*)gx_slot(tp, tape, i + 1, 0) : h;
+  };
+  float* hin = tape && d->layers > 0 ? (float*)gx_slot(tp, tape, 0, 0) : h;
 
   rc = gh_xf_group_moments(x, (int64_t)C * N, N, d->B, C, N, d->G, gn, ws + p.gnp, p.total - p.gnp, hip_stream);
   if (rc != GH_OK) return rc;
@@ -629,13 +711,13 @@ extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXf
   GhXfLinear a = {};
   a.T = T; a.K = C; a.N_out = M; a.prologue = GH_XF_PRO_GN; a.epilogue = GH_XF_EPI_BIAS_RES; a.rows_per_batch = N; a.groups = d->G;
   a.eps = d->gn_eps; a.x = x; a.x_stride = N; a.x_stride_b = (int64_t)C * N; a.w = stem->in_w; a.bias = stem->in_b; a.gamma = stem->gn_w;
-  a.beta = stem->gn_b; a.moments = gn; a.y = h; a.y_stride = M;
+  a.beta = stem->gn_b; a.moments = gn; a.y = hin; a.y_stride = M;
   rc = gh_xf_linear(&a, nullptr, 0, hip_stream);
   if (rc != GH_OK) return rc;
 
-  // y = epilogue(LN(h) w^T) or epilogue(src w^T)
+  // y = epilogue(LN(src) w^T) or epilogue(src w^T); ln: where the LayerNorm's row moments go
   auto product = [&](int pro, int epi, const float* src, int K, const float* gamma, const float* beta, const float* w, const float* bias,
-                     int n_out, const float* res, float* y) {
+                     int n_out, const float* res, float* y, void* ln) {
     GhXfLinear l = {};
     l.T = T; l.K = K; l.N_out = n_out; l.prologue = pro; l.epilogue = epi; l.eps = d->ln_eps; l.x = src; l.x_stride = K; l.w = w; l.bias = bias;
     l.gamma = gamma; l.beta = beta; l.res = res; l.res_stride = n_out; l.y = y; l.y_stride = n_out;
@@ -646,22 +728,657 @@ extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXf
     for (int which = 0; which < 2; ++which) {
       const float* wqkv = which ? L.qkv2 : L.qkv1;
       if (!wqkv) continue;
-      rc = product(GH_XF_PRO_LN, GH_XF_EPI_PLAIN, h, M, which ? L.ln2_w : L.ln1_w, which ? L.ln2_b : L.ln1_b, wqkv, nullptr, 3 * M, nullptr, qkv);
+      char* slot = tape ? gx_slot(tp, tape, i, which) : nullptr;
+      float* qkv = slot ? (float*)(slot + tp.a_qkv) : (float*)(ws + p.qkv);
+      float* att = slot ? (float*)(slot + tp.a_att) : (float*)(ws + p.att);
+      void* ln = slot ? (void*)(slot + tp.a_ln) : (void*)(ws + p.ln);
+      rc = product(GH_XF_PRO_LN, GH_XF_EPI_PLAIN, hin, M, which ? L.ln2_w : L.ln1_w, which ? L.ln2_b : L.ln1_b, wqkv, nullptr, 3 * M, nullptr, qkv, ln);
       if (rc != GH_OK) return rc;
-      rc = gh_xf_attention(qkv, 3 * M, d->B, N, d->heads, d->D, att, M, hip_stream);
+      rc = slot ? gh_xf_attention_lse(qkv, 3 * M, d->B, N, d->heads, d->D, att, M, (float*)(slot + tp.a_lse), hip_stream)
+                : gh_xf_attention(qkv, 3 * M, d->B, N, d->heads, d->D, att, M, hip_stream);
       if (rc != GH_OK) return rc;
-      rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, att, M, nullptr, nullptr, which ? L.o2_w : L.o1_w, which ? L.o2_b : L.o1_b, M, h, h);
+      float* hout = next(i, which);
+      rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, att, M, nullptr, nullptr, which ? L.o2_w : L.o1_w, which ? L.o2_b : L.o1_b, M, hin, hout, nullptr);
       if (rc != GH_OK) return rc;
+      hin = hout;
     }
-    rc = product(GH_XF_PRO_LN, GH_XF_EPI_GEGLU, h, M, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, 4 * M, nullptr, ff);
+    void* ln = tape ? (void*)(gx_slot(tp, tape, i, 2) + tp.f_ln) : (void*)(ws + p.ln);
+    rc = product(GH_XF_PRO_LN, GH_XF_EPI_GEGLU, hin, M, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, 4 * M, nullptr, ff, ln);
     if (rc != GH_OK) return rc;
-    rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, ff, 4 * M, nullptr, nullptr, L.ff2_w, L.ff2_b, M, h, h);
+    float* hout = next(i, 2);
+    rc = product(GH_XF_PRO_NONE, GH_XF_EPI_BIAS_RES, ff, 4 * M, nullptr, nullptr, L.ff2_w, L.ff2_b, M, hin, hout, nullptr);
     if (rc != GH_OK) return rc;
+    hin = hout;
   }
 
   GhXfLinear z = {};
-  z.T = T; z.K = M; z.N_out = C; z.prologue = GH_XF_PRO_NONE; z.epilogue = GH_XF_EPI_BIAS_RES_CF; z.rows_per_batch = N; z.x = h; z.x_stride = M;
+  z.T = T; z.K = M; z.N_out = C; z.prologue = GH_XF_PRO_NONE; z.epilogue = GH_XF_EPI_BIAS_RES_CF; z.rows_per_batch = N; z.x = hin; z.x_stride = M;
   z.w = stem->out_w; z.bias = stem->out_b; z.res = x; z.res_stride = N; z.res_stride_b = (int64_t)C * N; z.y = out; z.y_stride = N;
   z.y_stride_b = (int64_t)C * N;
   return gh_xf_linear(&z, nullptr, 0, hip_stream);
+}
+
+extern "C" int gh_xf_forward(const GhXfDims* d, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out, void* workspace,
+                             size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  return gx_forward(d, stem, layers, x, out, nullptr, workspace, ws_bytes, hip_stream);
+}
+
+extern "C" size_t gh_xf_tape_bytes(const GhXfDims* dims) {
+  bool empty;
+  if (gx_check_grad_dims(dims, &empty) != GH_OK || empty) return 0;
+  return gx_tape(dims).total;
+}
+
+extern "C" int gh_xf_forward_tape(const GhXfDims* d, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out, void* tape,
+                                  size_t tape_bytes, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_grad_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  if (!tape || !ghr_al16(tape)) return GH_ERR_INVALID_ARG;
+  if (tape_bytes < gx_tape(d).total) return GH_ERR_WORKSPACE_SMALL;
+  return gx_forward(d, stem, layers, x, out, (char*)tape, workspace, ws_bytes, hip_stream);
+}
+
+// ==== the backward to x, every weight frozen ============================================================================================
+static_assert(GH_XF_ATTN_BWD_ROWS == 32 * (GHR_BLOCK / 64) && GH_XF_ATTN_BWD_STAGE == 64, "a wave owns 32 rows; GhrSlab<2 ND, 8 ND> is 64 rows x D columns");
+static_assert(8 * GH_XF_GRAD_MAX_M <= GH_XF_MAX_K, "dn = [da | dg] W1 is a product of inner width 8M");
+
+// ---- attention: delta = dot(dout, out) per (row, head), one ascending chain -------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_attn_delta_kernel(const float* __restrict__ dout, long long dstride, const float* __restrict__ out,
+                                                                   long long ostride, long long T, int N, int H, int D, float* __restrict__ delta) {
+  const long long i = (long long)blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (i >= T * H) return;
+  const long long t = i / H, b = t / N, n = t - b * N;
+  const int h = (int)(i - t * H);
+  const float* a = dout + t * dstride + h * D;
+  const float* o = out + t * ostride + h * D;
+  float s = 0.f;
+  for (int d = 0; d < D; ++d) s = fmaf(a[d], o[d], s);
+  delta[(b * H + h) * N + n] = s;
+}
+
+// ---- attention: the query-block kernel owns dq -----------------------------------------------------------------------------------------
+// The forward's shape: the query on the lane, K and V from LDS 64 keys a stage; every wave folds both tiles of 32 keys of a stage, in
+// ascending order, so a query's dq is one chain over all keys. `block` is the workgroup's index among the query blocks.
+template <int ND>
+__device__ __forceinline__ void gx_attn_dq(int block, float* s_stage, const float* __restrict__ qkv, long long stride, const float* __restrict__ dout,
+                                           long long dstride, const float* __restrict__ lse, const float* __restrict__ delta,
+                                           float* __restrict__ dqkv, long long gstride, int N, int H, float scale, int vec, int ntiles) {
+  constexpr int D = 32 * ND, P = D + 1;
+  float* s_k = s_stage;
+  float* s_v = s_stage + GH_XF_ATTN_BWD_STAGE * P;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int qt = block % ntiles, bh = block / ntiles, b = bh / H, h = bh - b * H;
+  const int M = H * D;
+  const float* q = qkv + (long long)b * N * stride + h * D;
+  const float* k = q + M;
+  const float* v = q + 2 * M;
+  const float* go = dout + (long long)b * N * dstride + h * D;
+  const int row = qt * GH_XF_ATTN_BWD_ROWS + 32 * wave + col;
+  const bool live = row < N, wave_live = qt * GH_XF_ATTN_BWD_ROWS + 32 * wave < N;
+
+  float qr[16 * ND], gr[16 * ND];
+#pragma unroll
+  for (int s = 0; s < 16 * ND; ++s) {
+    qr[s] = live ? q[(long long)row * stride + 2 * s + half] : 0.f;
+    gr[s] = live ? go[(long long)row * dstride + 2 * s + half] : 0.f;
+  }
+  const float ls = live ? lse[(long long)bh * N + row] : 0.f, dl = live ? delta[(long long)bh * N + row] : 0.f;
+  ghr_acc dq[ND];
+#pragma unroll
+  for (int t = 0; t < ND; ++t) dq[t] = gx_splat(0.f);
+
+  GhrSlab<2 * ND, 8 * ND> ks, vs;                              // 64 keys x D columns each; rows past N arrive as zeros
+  ghr_fetch_in(ks, k, stride, 0, 0, N, D, vec, tid);
+  ghr_fetch_in(vs, v, stride, 0, 0, N, D, vec, tid);
+  for (int kt = 0; kt < N; kt += GH_XF_ATTN_BWD_STAGE) {
+    __syncthreads();                                           // the previous stage has been read by every wave
+    ghr_put(ks, s_k, P, tid);
+    ghr_put(vs, s_v, P, tid);
+    __syncthreads();
+    if (kt + GH_XF_ATTN_BWD_STAGE < N) {
+      ghr_fetch_in(ks, k, stride, kt + GH_XF_ATTN_BWD_STAGE, 0, N, D, vec, tid);
+      ghr_fetch_in(vs, v, stride, kt + GH_XF_ATTN_BWD_STAGE, 0, N, D, vec, tid);
+    }
+    if (!wave_live) continue;                                  // wave-uniform; the barriers above are met by every wave
+#pragma unroll 1
+    for (int sub = 0; sub < GH_XF_ATTN_BWD_STAGE; sub += 32) {
+      if (kt + sub >= N) break;                                // wave-uniform: the tile holds no key
+      ghr_acc st = gx_splat(0.f), dp = gx_splat(0.f);
+      const float* ap = s_k + (sub + col) * P + half;
+      const float* vp = s_v + (sub + col) * P + half;
+#pragma unroll
+      for (int s = 0; s < 16 * ND; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], qr[s], st, 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 16 * ND; ++s) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[2 * s], gr[s], dp, 0, 0, 0);
+      float ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = expf(st[r] * scale - ls);
+        ds[r] = kt + sub + ghr_acc_row(r, half) < N ? (p * (dp[r] - dl)) * scale : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          dq[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_k[(sub + ghr_acc_row(r, half)) * P + 32 * t + col], ds[r], dq[t], 0, 0, 0);
+      }
+    }
+  }
+  if (live) {
+    float* dst = dqkv + ((long long)b * N + row) * gstride + h * D;
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[32 * t + ghr_acc_row(r, half)] = dq[t][r];
+    }
+  }
+}
+
+// ---- attention: the key-block kernel owns dk and dv ------------------------------------------------------------------------------------
+// The key on the lane; q and dout rows cross LDS 64 queries a stage with their lse and delta (s_ld: lse, then delta, of the stage's
+// queries). `block` is the workgroup's index among the key blocks.
+template <int ND>
+__device__ __forceinline__ void gx_attn_dkv(int block, float* s_stage, float* s_ld, const float* __restrict__ qkv, long long stride,
+                                            const float* __restrict__ dout, long long dstride, const float* __restrict__ lse,
+                                            const float* __restrict__ delta, float* __restrict__ dqkv, long long gstride, int N, int H, float scale,
+                                            int vec, int vec_d, int ntiles) {
+  constexpr int D = 32 * ND, P = D + 1;
+  float* s_q = s_stage;
+  float* s_g = s_stage + GH_XF_ATTN_BWD_STAGE * P;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int ktile = block % ntiles, bh = block / ntiles, b = bh / H, h = bh - b * H;
+  const int M = H * D;
+  const float* q = qkv + (long long)b * N * stride + h * D;
+  const float* k = q + M;
+  const float* v = q + 2 * M;
+  const float* go = dout + (long long)b * N * dstride + h * D;
+  const int row = ktile * GH_XF_ATTN_BWD_ROWS + 32 * wave + col;
+  const bool live = row < N, wave_live = ktile * GH_XF_ATTN_BWD_ROWS + 32 * wave < N;
+
+  float kr[16 * ND], vr[16 * ND];
+#pragma unroll
+  for (int s = 0; s < 16 * ND; ++s) {
+    kr[s] = live ? k[(long long)row * stride + 2 * s + half] : 0.f;
+    vr[s] = live ? v[(long long)row * stride + 2 * s + half] : 0.f;
+  }
+  ghr_acc dk[ND], dv[ND];
+#pragma unroll
+  for (int t = 0; t < ND; ++t) {
+    dk[t] = gx_splat(0.f);
+    dv[t] = gx_splat(0.f);
+  }
+
+  // thread i < 64 carries lse of the stage's query i, thread 64 + i its delta
+  const float* ldsrc = (tid < GH_XF_ATTN_BWD_STAGE ? lse : delta) + (long long)bh * N;
+  const int ldi = tid & (GH_XF_ATTN_BWD_STAGE - 1);
+  GhrSlab<2 * ND, 8 * ND> qs, gs;                              // 64 queries x D columns each; rows past N arrive as zeros
+  ghr_fetch_in(qs, q, stride, 0, 0, N, D, vec, tid);
+  ghr_fetch_in(gs, go, dstride, 0, 0, N, D, vec_d, tid);
+  float ld = tid < 2 * GH_XF_ATTN_BWD_STAGE && ldi < N ? ldsrc[ldi] : 0.f;
+  for (int qt = 0; qt < N; qt += GH_XF_ATTN_BWD_STAGE) {
+    __syncthreads();                                           // the previous stage has been read by every wave
+    ghr_put(qs, s_q, P, tid);
+    ghr_put(gs, s_g, P, tid);
+    if (tid < 2 * GH_XF_ATTN_BWD_STAGE) s_ld[tid] = ld;
+    __syncthreads();
+    if (qt + GH_XF_ATTN_BWD_STAGE < N) {
+      ghr_fetch_in(qs, q, stride, qt + GH_XF_ATTN_BWD_STAGE, 0, N, D, vec, tid);
+      ghr_fetch_in(gs, go, dstride, qt + GH_XF_ATTN_BWD_STAGE, 0, N, D, vec_d, tid);
+      ld = tid < 2 * GH_XF_ATTN_BWD_STAGE && qt + GH_XF_ATTN_BWD_STAGE + ldi < N ? ldsrc[qt + GH_XF_ATTN_BWD_STAGE + ldi] : 0.f;
+    }
+    if (!wave_live) continue;                                  // wave-uniform; the barriers above are met by every wave
+#pragma unroll 1
+    for (int sub = 0; sub < GH_XF_ATTN_BWD_STAGE; sub += 32) {
+      if (qt + sub >= N) break;                                // wave-uniform: the tile holds no query
+      ghr_acc st = gx_splat(0.f), dp = gx_splat(0.f);
+      const float* ap = s_q + (sub + col) * P + half;
+      const float* gp = s_g + (sub + col) * P + half;
+#pragma unroll
+      for (int s = 0; s < 16 * ND; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], kr[s], st, 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 16 * ND; ++s) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gp[2 * s], vr[s], dp, 0, 0, 0);
+      float p[16], ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qrow = sub + ghr_acc_row(r, half);
+        const bool ok = qt + qrow < N;                         // a query past N contributes exactly 0, whatever lse holds there
+        const float pv = expf(st[r] * scale - s_ld[qrow]);
+        p[r] = ok ? pv : 0.f;
+        ds[r] = ok ? (pv * (dp[r] - s_ld[GH_XF_ATTN_BWD_STAGE + qrow])) * scale : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < ND; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int o = (sub + ghr_acc_row(r, half)) * P + 32 * t + col;
+          dv[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_g[o], p[r], dv[t], 0, 0, 0);
+          dk[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_q[o], ds[r], dk[t], 0, 0, 0);
+        }
+      }
+    }
+  }
+  if (live) {                                                  // a key past N: its rows are not written
+    float* dst = dqkv + ((long long)b * N + row) * gstride + M + h * D;
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        dst[32 * t + ghr_acc_row(r, half)] = dk[t][r];
+        dst[M + 32 * t + ghr_acc_row(r, half)] = dv[t][r];
+      }
+    }
+  }
+}
+
+// One launch holds both kinds of workgroup: the first nkv own a key block each (dk, dv), the rest a query block each (dq). Neither kind
+// reads what the other writes, so no workgroup waits for another; at B = 1 either kind alone would fill half the chip.
+template <int ND>
+__global__ __launch_bounds__(GHR_BLOCK) void gx_attn_bwd_kernel(const float* __restrict__ qkv, long long stride, const float* __restrict__ dout,
+                                                                 long long dstride, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                 float* __restrict__ dqkv, long long gstride, int N, int H, float scale, int vec,
+                                                                 int vec_d, int ntiles, int nkv) {
+  __shared__ float s_stage[2 * GH_XF_ATTN_BWD_STAGE * (32 * ND + 1)];
+  __shared__ float s_ld[2 * GH_XF_ATTN_BWD_STAGE];
+  if ((int)blockIdx.x < nkv) {                                 // workgroup-uniform
+    gx_attn_dkv<ND>((int)blockIdx.x, s_stage, s_ld, qkv, stride, dout, dstride, lse, delta, dqkv, gstride, N, H, scale, vec, vec_d, ntiles);
+  } else {
+    gx_attn_dq<ND>((int)blockIdx.x - nkv, s_stage, qkv, stride, dout, dstride, lse, delta, dqkv, gstride, N, H, scale, vec, ntiles);
+  }
+}
+
+// ---- the feed-forward: [da | dg] in one pass --------------------------------------------------------------------------------------------
+// gx_linear_kernel with two X slabs (the cotangent g, and h through LN3) and three W slabs for the same 64 x 64 tile of the F = 4M inner
+// columns: du = g . W2 over w2t's rows, a and g' as the forward's GEGLU epilogue forms them.
+__global__ __launch_bounds__(GHR_BLOCK) void gx_geglu_bwd_kernel(const float* __restrict__ g, long long g_stride, const float* __restrict__ h,
+                                                                  long long h_stride, const float* __restrict__ mom, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, const float* __restrict__ w1,
+                                                                  const float* __restrict__ b1, const float* __restrict__ w2t, float* __restrict__ y,
+                                                                  long long y_stride, int T, int M, int vec_g, int vec_h, int vec_w1, int vec_w2,
+                                                                  int ncol_tiles) {
+  __shared__ float s_all[2 * GX_TR * GX_P + 3 * GX_TC * GX_P];
+  float* s_g = s_all;
+  float* s_h = s_all + GX_TR * GX_P;
+  float* s_wu = s_all + 2 * GX_TR * GX_P;
+  float* s_wa = s_wu + GX_TC * GX_P;
+  float* s_wg = s_wa + GX_TC * GX_P;
+  const int F = 4 * M;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int tc = blockIdx.x % ncol_tiles, tr = blockIdx.x / ncol_tiles;
+  const int row0 = tr * GX_TR, c0 = tc * GX_TC;
+
+  float ln[2][2] = {{0.f, 1.f}, {0.f, 1.f}};
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int r = row0 + (tid + it * GHR_BLOCK) / 8;
+    if (r < T) {
+      ln[it][0] = mom[2 * (long long)r];
+      ln[it][1] = mom[2 * (long long)r + 1];
+    }
+  }
+  const int j = c0 + 32 * wc + col;                            // the lane's inner column: F is a multiple of 128, so j < F
+  ghr_acc du = gx_splat(0.f), aa = gx_splat(b1[j]), ag = gx_splat(b1[F + j]);
+
+  GhrSlab<2, 8> xg, xh, wu, wa, wg;
+  auto fetch = [&](int k0) {
+    ghr_fetch_in(xg, g, g_stride, row0, k0, T, M, vec_g, tid);
+    ghr_fetch_in(xh, h, h_stride, row0, k0, T, M, vec_h, tid);
+    ghr_fetch_in(wu, w2t, M, c0, k0, F, M, vec_w2, tid);
+    ghr_fetch_in(wa, w1, M, c0, k0, F, M, vec_w1, tid);
+    ghr_fetch_in(wg, w1 + (long long)F * M, M, c0, k0, F, M, vec_w1, tid);
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < M; k0 += GX_KS) {
+    __syncthreads();                                           // the previous slab has been read by every wave
+    ghr_put(xg, s_g, GX_P, tid);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {                           // the LayerNorm on the way in, as gx_put_x<PRO_LN>
+      const int i = tid + it * GHR_BLOCK, r = i / 8, c = 4 * (i % 8);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) s_h[r * GX_P + c + jj] = ((xh.v[it][jj] - ln[it][0]) * ln[it][1]) * gamma[k0 + c + jj] + beta[k0 + c + jj];
+    }
+    ghr_put(wu, s_wu, GX_P, tid);
+    ghr_put(wa, s_wa, GX_P, tid);
+    ghr_put(wg, s_wg, GX_P, tid);
+    __syncthreads();
+    if (k0 + GX_KS < M) fetch(k0 + GX_KS);
+    const int ao = (32 * wr + col) * GX_P + half, bo = (32 * wc + col) * GX_P + half;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float hv = s_h[ao + 2 * s];
+      du = __builtin_amdgcn_mfma_f32_32x32x2f32(s_g[ao + 2 * s], s_wu[bo + 2 * s], du, 0, 0, 0);
+      aa = __builtin_amdgcn_mfma_f32_32x32x2f32(hv, s_wa[bo + 2 * s], aa, 0, 0, 0);
+      ag = __builtin_amdgcn_mfma_f32_32x32x2f32(hv, s_wg[bo + 2 * s], ag, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long long t = row0 + 32 * wr + ghr_acc_row(r, half);
+    if (t < T) {
+      const float gv = ag[r], e = 1.0f + erff(gv * 0.70710678118654752440f);
+      const float gelu = (0.5f * gv) * e;
+      const float dgelu = 0.5f * e + (gv * 0.39894228f) * expf((-0.5f * gv) * gv);
+      y[t * y_stride + j] = du[r] * gelu;
+      y[t * y_stride + F + j] = (du[r] * aa[r]) * dgelu;
+    }
+  }
+}
+
+// ---- LayerNorm: one wave per row, g += the norm's backward of dn ---------------------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_ln_bwd_kernel(const float* __restrict__ dn, long long dn_stride, const float* __restrict__ x,
+                                                               long long x_stride, const float* __restrict__ mom, const float* __restrict__ gamma,
+                                                               int T, int K, float* __restrict__ g, long long g_stride) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long row = (long long)blockIdx.x * GX_LN_ROWS + wave;
+  if (row >= T) return;                                        // wave-uniform; the kernel has no barrier
+  const float* dr = dn + row * dn_stride;
+  const float* xr = x + row * x_stride;
+  float* gr = g + row * g_stride;
+  const float mean = mom[2 * row], rstd = mom[2 * row + 1];
+  float s1 = 0.f, s2 = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float w = dr[k] * gamma[k], xh = (xr[k] - mean) * rstd;
+    s1 += w;
+    s2 = fmaf(w, xh, s2);
+  }
+  s1 = gx_wave_sum(s1) / (float)K;
+  s2 = gx_wave_sum(s2) / (float)K;
+  for (int k = lane; k < K; k += 64) {
+    const float w = dr[k] * gamma[k], xh = (xr[k] - mean) * rstd;
+    gr[k] = gr[k] + rstd * ((w - s1) - xh * s2);
+  }
+}
+
+// ---- GroupNorm: the two sums per (batch, group), then the element-wise pass ---------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_gn_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                    const float* __restrict__ mom, const float* __restrict__ gamma, int C, int N,
+                                                                    int G, int cpg, int nchunks, float eps, float* __restrict__ part) {
+  __shared__ float s_red[4];
+  const int chunk = blockIdx.x % nchunks, bg = blockIdx.x / nchunks, b = bg / G, gi = bg - b * G;
+  const int n = chunk * GH_XF_GN_CHUNK + threadIdx.x;
+  const long long base = ((long long)b * C + (long long)gi * cpg) * N + n;
+  const float mean = mom[2 * (long long)bg], rstd = 1.0f / sqrtf(mom[2 * (long long)bg + 1] / ((float)cpg * (float)N) + eps);
+  float s1 = 0.f, s2 = 0.f;
+  if (n < N) {
+    for (int c = 0; c < cpg; ++c) {
+      const float w = dy[base + (long long)c * N] * gamma[gi * cpg + c], xh = (x[base + (long long)c * N] - mean) * rstd;
+      s1 += w;
+      s2 = fmaf(w, xh, s2);
+    }
+  }
+  const float t1 = gx_block_sum(s1, s_red), t2 = gx_block_sum(s2, s_red);
+  if (threadIdx.x == 0) {
+    part[2 * (long long)blockIdx.x] = t1;
+    part[2 * (long long)blockIdx.x + 1] = t2;
+  }
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_gn_bwd_join_kernel(const float* __restrict__ part, int BG, int nchunks, float* __restrict__ sums) {
+  const int bg = blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (bg >= BG) return;
+  const float* p = part + 2 * (long long)bg * nchunks;
+  float s1 = p[0], s2 = p[1];
+  for (int c = 1; c < nchunks; ++c) {
+    s1 += p[2 * c];
+    s2 += p[2 * c + 1];
+  }
+  sums[2 * bg] = s1;
+  sums[2 * bg + 1] = s2;
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_gn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                     const float* __restrict__ mom, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ sums, const float* __restrict__ dout,
+                                                                     float* __restrict__ dx, int C, int N, int G, int cpg, int nchunks, float eps) {
+  const int chunk = blockIdx.x % nchunks, bc = blockIdx.x / nchunks, b = bc / C, c = bc - b * C;
+  const int n = chunk * GH_XF_GN_CHUNK + threadIdx.x;
+  if (n >= N) return;
+  const long long bg = (long long)b * G + c / cpg, i = (long long)bc * N + n;
+  const float cnt = (float)cpg * (float)N;
+  const float mean = mom[2 * bg], rstd = 1.0f / sqrtf(mom[2 * bg + 1] / cnt + eps);
+  const float s1 = sums[2 * bg] / cnt, s2 = sums[2 * bg + 1] / cnt;
+  const float w = dy[i] * gamma[c], xh = (x[i] - mean) * rstd;
+  dx[i] = dout[i] + rstd * ((w - s1) - xh * s2);
+}
+
+// ---- host: the single launches of the backward -----------------------------------------------------------------------------------------
+extern "C" size_t gh_xf_attention_backward_workspace_bytes(int B, int N, int heads) {
+  if (B <= 0 || N <= 0 || heads <= 0 || (long long)B * N > GH_XF_MAX_T || heads > GH_XF_MAX_M / 32) return 0;
+  return ghr_align((size_t)B * N * heads * sizeof(float));
+}
+
+extern "C" int gh_xf_attention_backward(const float* qkv, int64_t qkv_stride, const float* out, int64_t out_stride, const float* lse,
+                                        const float* dout, int64_t dout_stride, int B, int N, int heads, int D, float* dqkv,
+                                        int64_t dqkv_stride, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  int grid = 0;
+  int rc = gx_check_attn(B, N, heads, D, &grid, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  const int M = heads * D, nt = (N + GH_XF_ATTN_BWD_ROWS - 1) / GH_XF_ATTN_BWD_ROWS;
+  if (gx_tiles(2LL * B * heads, nt, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;   // key blocks, then query blocks
+  const int nkv = grid / 2;
+  const float* in[] = {qkv, out, lse, dout};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!dqkv || !ghr_al4(dqkv) || qkv_stride < 3 * M || out_stride < M || dout_stride < M || dqkv_stride < 3 * M) return GH_ERR_INVALID_ARG;
+  if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (ws_bytes < gh_xf_attention_backward_workspace_bytes(B, N, heads)) return GH_ERR_WORKSPACE_SMALL;
+  float* delta = (float*)workspace;
+  const int vec = ghr_al16(qkv) && qkv_stride % 4 == 0, vec_d = ghr_al16(dout) && dout_stride % 4 == 0;
+  const float scale = (float)(1.0 / sqrt((double)D));
+  const long long T = (long long)B * N;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_attn_delta_kernel, dim3((unsigned)((T * heads + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, dout,
+                     (long long)dout_stride, out, (long long)out_stride, T, N, heads, D, delta);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  if (D == 32) {
+    hipLaunchKernelGGL(gx_attn_bwd_kernel<1>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, dout, (long long)dout_stride,
+                       lse, (const float*)delta, dqkv, (long long)dqkv_stride, N, heads, scale, vec, vec_d, nt, nkv);
+  } else {
+    hipLaunchKernelGGL(gx_attn_bwd_kernel<2>, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, qkv, (long long)qkv_stride, dout, (long long)dout_stride,
+                       lse, (const float*)delta, dqkv, (long long)dqkv_stride, N, heads, scale, vec, vec_d, nt, nkv);
+  }
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+extern "C" int gh_xf_geglu_backward(const float* g, int64_t g_stride, const float* h, int64_t h_stride, const float* moments, const float* gamma,
+                                    const float* beta, const float* w1, const float* b1, const float* w2t, int T, int M, float* y,
+                                    int64_t y_stride, void* hip_stream) {
+  if (T < 0 || M < 1) return GH_ERR_INVALID_ARG;
+  if (M % 32 != 0 || M > GH_XF_MAX_M || T > GH_XF_MAX_T) return GH_ERR_UNSUPPORTED;
+  if (T == 0) return GH_OK;
+  int grid;
+  const int ncol = 4 * M / GX_TC;
+  if (gx_tiles(ncol, (T + GX_TR - 1) / GX_TR, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;
+  const float* in[] = {g, h, moments, gamma, beta, w1, b1, w2t};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!y || !ghr_al4(y) || g_stride < M || h_stride < M || y_stride < 8 * (int64_t)M) return GH_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_geglu_bwd_kernel, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, g, (long long)g_stride, h, (long long)h_stride, moments, gamma,
+                     beta, w1, b1, w2t, y, (long long)y_stride, T, M, (int)(ghr_al16(g) && g_stride % 4 == 0), (int)(ghr_al16(h) && h_stride % 4 == 0),
+                     (int)ghr_al16(w1), (int)ghr_al16(w2t), ncol);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+extern "C" int gh_xf_layernorm_backward(const float* dn, int64_t dn_stride, const float* x, int64_t x_stride, const float* moments,
+                                        const float* gamma, int T, int K, float* g, int64_t g_stride, void* hip_stream) {
+  if (T < 0 || K < 1) return GH_ERR_INVALID_ARG;
+  if (T > GH_XF_MAX_T || K > GH_XF_MAX_K) return GH_ERR_UNSUPPORTED;
+  if (T == 0) return GH_OK;
+  const float* in[] = {dn, x, moments, gamma};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!g || !ghr_al4(g) || dn_stride < K || x_stride < K || g_stride < K) return GH_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_ln_bwd_kernel, dim3((unsigned)((T + GX_LN_ROWS - 1) / GX_LN_ROWS)), dim3(GHR_BLOCK), 0, s, dn, (long long)dn_stride, x,
+                     (long long)x_stride, moments, gamma, T, K, g, (long long)g_stride);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+static int gx_check_gn_bwd(int B, int C, int N, int G, bool* empty) {
+  const int rc = gx_check_groups(B, C, N, G, empty);
+  if (rc != GH_OK || *empty) return rc;
+  int grid;
+  if (gx_tiles((long long)B * C, (N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, &grid) != GH_OK) { *empty = true; return GH_ERR_UNSUPPORTED; }
+  return GH_OK;
+}
+
+// the chunks' partial sums (B G nchunks, 2), then the joined sums (B G, 2)
+extern "C" size_t gh_xf_group_norm_backward_workspace_bytes(int B, int C, int N, int G) {
+  bool empty;
+  if (gx_check_gn_bwd(B, C, N, G, &empty) != GH_OK || empty) return 0;
+  return ghr_align((size_t)B * G * ((N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK) * 2 * sizeof(float)) + ghr_align((size_t)B * G * 2 * sizeof(float));
+}
+
+extern "C" int gh_xf_group_norm_backward(const float* dy, const float* x, const float* moments, const float* gamma, const float* dout, float* dx,
+                                         int B, int C, int N, int G, float eps, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_gn_bwd(B, C, N, G, &empty);
+  if (rc != GH_OK) return rc;
+  if (!(eps >= 0.f && isfinite(eps))) return GH_ERR_INVALID_ARG;
+  if (empty) return GH_OK;
+  const float* in[] = {dy, x, moments, gamma, dout};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!dx || !ghr_al4(dx) || dx == dy || dx == x || dx == dout || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (ws_bytes < gh_xf_group_norm_backward_workspace_bytes(B, C, N, G)) return GH_ERR_WORKSPACE_SMALL;
+  const int nchunks = (N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK, BG = B * G, cpg = C / G;
+  float* part = (float*)workspace;
+  float* sums = (float*)((char*)workspace + ghr_align((size_t)BG * nchunks * 2 * sizeof(float)));
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_gn_bwd_part_kernel, dim3((unsigned)(BG * nchunks)), dim3(GHR_BLOCK), 0, s, dy, x, moments, gamma, C, N, G, cpg, nchunks, eps,
+                     part);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  hipLaunchKernelGGL(gx_gn_bwd_join_kernel, dim3((unsigned)((BG + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, (const float*)part, BG, nchunks,
+                     sums);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  hipLaunchKernelGGL(gx_gn_bwd_apply_kernel, dim3((unsigned)(B * C * nchunks)), dim3(GHR_BLOCK), 0, s, dy, x, moments, gamma, (const float*)sums, dout,
+                     dx, C, N, G, cpg, nchunks, eps);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+// ---- host: the whole backward ------------------------------------------------------------------------------------------------------------
+// the workspace: the stream's cotangent g (T, M), dn (T, M), wide (T, 8M) — [da | dg], or datt (T, M) followed by dqkv (T, 3M) —, the
+// attention's delta, dy (B, C, N) of the GroupNorm, and the GroupNorm's partial sums
+struct GxBackPlan {
+  size_t g, dn, wide, delta, dy, gnw, total;
+};
+
+static GxBackPlan gx_back_plan(const GhXfDims* d) {
+  const size_t T = (size_t)d->B * d->N, M = (size_t)d->heads * d->D, f = sizeof(float);
+  GxBackPlan p;
+  size_t at = 0;
+  p.g = at; at += ghr_align(T * M * f);
+  p.dn = at; at += ghr_align(T * M * f);
+  p.wide = at; at += ghr_align(T * 8 * M * f);
+  p.delta = at; at += gh_xf_attention_backward_workspace_bytes(d->B, d->N, d->heads);
+  p.dy = at; at += ghr_align(T * d->C * f);
+  p.gnw = at; at += gh_xf_group_norm_backward_workspace_bytes(d->B, d->C, d->N, d->G);
+  p.total = at;
+  return p;
+}
+
+extern "C" size_t gh_xf_backward_workspace_bytes(const GhXfDims* dims) {
+  bool empty;
+  if (gx_check_grad_dims(dims, &empty) != GH_OK || empty) return 0;
+  return gx_back_plan(dims).total;
+}
+
+extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape_,
+                              const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  int rc = gx_check_grad_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  if (!stem || (d->layers > 0 && !layers) || !x || !dout || !dx || dx == x || dx == dout || !ghr_al4(x) || !ghr_al4(dout) || !ghr_al4(dx))
+    return GH_ERR_INVALID_ARG;
+  const float* sp[] = {stem->gn_w, stem->in_t, stem->out_t};
+  for (const float* p : sp) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < d->layers; ++i) {
+    const GhXfLayerT& L = layers[i];
+    const float* need[] = {L.ln1_w, L.qkv1_t, L.o1_t, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, L.ff1_t, L.ff2_t};
+    for (const float* p : need) {
+      if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+    }
+    if (L.qkv2_t && (!ghr_al4(L.qkv2_t) || !L.ln2_w || !ghr_al4(L.ln2_w) || !L.o2_t || !ghr_al4(L.o2_t))) return GH_ERR_INVALID_ARG;
+  }
+  if (!tape_ || !ghr_al16(tape_) || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  const GxBackPlan p = gx_back_plan(d);
+  if (ws_bytes < p.total) return GH_ERR_WORKSPACE_SMALL;
+  const GxTape tp = gx_tape(d);
+  char* tape = (char*)tape_;                                   // read only
+  char* ws = (char*)workspace;
+  float* g = (float*)(ws + p.g);
+  float* dn = (float*)(ws + p.dn);
+  float* wide = (float*)(ws + p.wide);
+  float* dy = (float*)(ws + p.dy);
+  const int T = d->B * d->N, M = d->heads * d->D, C = d->C, N = d->N;
+
+  // y (T, n_out) = src (T, K) . wt^T, each element one ascending chain from zero
+  auto data = [&](const float* src, int K, const float* wt, int n_out, float* y) {
+    GhXfLinear l = {};
+    l.T = T; l.K = K; l.N_out = n_out; l.prologue = GH_XF_PRO_NONE; l.epilogue = GH_XF_EPI_PLAIN; l.x = src; l.x_stride = K; l.w = wt; l.y = y;
+    l.y_stride = n_out;
+    return gh_xf_linear(&l, nullptr, 0, hip_stream);
+  };
+
+  GhXfLinear a = {};                                           // g = dout_rows . W_out, dout read channel first in place
+  a.T = T; a.K = C; a.N_out = M; a.prologue = GH_XF_PRO_CF; a.epilogue = GH_XF_EPI_PLAIN; a.rows_per_batch = N; a.x = dout; a.x_stride = N;
+  a.x_stride_b = (int64_t)C * N; a.w = stem->out_t; a.y = g; a.y_stride = M;
+  rc = gh_xf_linear(&a, nullptr, 0, hip_stream);
+  if (rc != GH_OK) return rc;
+
+  for (int i = d->layers - 1; i >= 0; --i) {
+    const GhXfLayerT& L = layers[i];
+    const char* fs = gx_slot(tp, tape, i, 2);
+    rc = gh_xf_geglu_backward(g, M, (const float*)fs, M, (const float*)(fs + tp.f_ln), L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, L.ff2_t, T, M, wide,
+                              8 * (int64_t)M, hip_stream);
+    if (rc != GH_OK) return rc;
+    rc = data(wide, 8 * M, L.ff1_t, M, dn);
+    if (rc != GH_OK) return rc;
+    rc = gh_xf_layernorm_backward(dn, M, (const float*)fs, M, (const float*)(fs + tp.f_ln), L.ln3_w, T, M, g, M, hip_stream);
+    if (rc != GH_OK) return rc;
+    for (int which = 1; which >= 0; --which) {
+      const float* wqkv_t = which ? L.qkv2_t : L.qkv1_t;
+      if (!wqkv_t) continue;
+      const char* as = gx_slot(tp, tape, i, which);
+      float* datt = wide;
+      float* dqkv = wide + (size_t)T * M;
+      rc = data(g, M, which ? L.o2_t : L.o1_t, M, datt);
+      if (rc != GH_OK) return rc;
+      rc = gh_xf_attention_backward((const float*)(as + tp.a_qkv), 3 * M, (const float*)(as + tp.a_att), M, (const float*)(as + tp.a_lse), datt, M,
+                                    d->B, N, d->heads, d->D, dqkv, 3 * M, ws + p.delta, p.dy - p.delta, hip_stream);
+      if (rc != GH_OK) return rc;
+      rc = data(dqkv, 3 * M, wqkv_t, M, dn);
+      if (rc != GH_OK) return rc;
+      rc = gh_xf_layernorm_backward(dn, M, (const float*)as, M, (const float*)(as + tp.a_ln), which ? L.ln2_w : L.ln1_w, T, M, g, M, hip_stream);
+      if (rc != GH_OK) return rc;
+    }
+  }
+
+  GhXfLinear z = {};                                           // dy = g . W_in, written channel first; neither bias nor residual
+  z.T = T; z.K = M; z.N_out = C; z.prologue = GH_XF_PRO_NONE; z.epilogue = GH_XF_EPI_BIAS_RES_CF; z.rows_per_batch = N; z.x = g; z.x_stride = M;
+  z.w = stem->in_t; z.y = dy; z.y_stride = N; z.y_stride_b = (int64_t)C * N;
+  rc = gx_linear(&z, nullptr, 0, hip_stream, false);
+  if (rc != GH_OK) return rc;
+  return gh_xf_group_norm_backward(dy, x, (const float*)(tape + tp.gn), stem->gn_w, dout, dx, d->B, C, N, d->G, d->gn_eps, ws + p.gnw,
+                                   p.total - p.gnw, hip_stream);
 }

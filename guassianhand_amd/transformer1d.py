@@ -1,24 +1,34 @@
 """The Transformer1D backbones (tgs/models/transformers.py:673-908, called at infer_one_shot.py:256-264): a GroupNorm, proj_in, a stack
 of blocks — self-attention, a second attention over the same tokens where `attn2` exists, a GEGLU feed-forward, each behind a
-LayerNorm and added to the stream — and proj_out back to channel-first plus the input. Forward only in HIP, through include/gh_xf.h:
+LayerNorm and added to the stream — and proj_out back to channel-first plus the input. In HIP through include/gh_xf.h: the forward,
+and opt-in the backward to the input with every weight frozen:
 
-    transformer1d(module_or_params, x, ops="fused")     x (B, C, N) float32 -> (B, C, N)
+    transformer1d(module_or_params, x, ops="fused", grad="none")     x (B, C, N) float32 -> (B, C, N)
 
 The kernel path is for frozen inference: one host call enqueues the whole stack (4 + 11 launches per layer), float32 throughout, no
 atomics, bitwise reproducible. It runs when `kernel_reason` finds nothing against it: float32 tensors on a ROCm device outside
 autocast, no gradient wanted (grad mode off, or neither x nor any parameter requires one), no encoder_hidden_states and no mask,
 LayerNorm blocks with affine norms, GEGLU, no attention bias, no only_cross_attention, no gated fuser, no feed-forward chunking,
 dropout inactive, and sizes the kernels take (D in {32, 64}, M = heads * D <= 1024, C a multiple of the group count and of 32,
-C <= 1024). In every other case — the one-shot fit that trains the identity code through the texture backbone is one — the forward is
-the base class's own (`fuse_transformer1d`, the config seam) or `transformer1d_ref` (the standalone module, the function form), with
-every gradient. There is no backward kernel.
+C <= 1024). In every other case the forward is the base class's own (`fuse_transformer1d`, the config seam) or `transformer1d_ref`
+(the standalone module, the function form), with every gradient.
+
+grad="input" (the keyword of `transformer1d`, `kernel_reason`, `Transformer1D.forward`, `fused_transformer1d_cls` and
+`fuse_transformer1d`) adds the case the one-shot fit needs, which trains the identity code through the frozen texture backbone: where
+grad mode is on, x requires a gradient and no parameter does, the call is a torch.autograd.Function whose forward is
+gh_xf_forward_tape (the same kernels, `out` bitwise the same, plus a tape of about 11 M T floats a layer) and whose backward is
+gh_xf_backward: 5 + 13 launches per layer, float32, no atomics, bitwise reproducible, once differentiable. It takes M <= 512
+(GH_XF_GRAD_MAX_M). A parameter that requires a gradient is the reason "a parameter wants a gradient" and the torch path; with nothing
+requiring a gradient the plain untaped kernels run. grad="none", the default, is the forward-only behaviour exactly.
 
 `transformer1d_ref(params, x, acc=None)` is the plain-torch restatement with an explicit softmax, so that it runs in float64 (the
 yardstick of the GPU tests); it is written from transformers.py and the attribute layout of diffusers' Attention and is not pinned
 against a recorded run of the reference. `params_of(module)` reads the nested parameter dict off any module with that layout.
 `Transformer1D` is the module standalone with the reference's state-dict keys. `fuse_transformer1d(module)` swaps a built module's
 class for `fused_transformer1d_cls` of its own class; the concatenated [Wq; Wk; Wv] are cached per module and rebuilt when a
-parameter's version counter (or storage) changes; `refresh(module)` drops them by hand. `linear`, `group_moments` and `attention` are the single launches."""
+parameter's version counter (or storage) changes, and so are the transposed copies the backward's data products read, built when a
+backward first needs them; `refresh(module)` drops them by hand. `linear`, `group_moments` and `attention` are the forward's single
+launches; `attention_lse`, `attention_backward`, `geglu_backward`, `layernorm_backward` and `group_norm_backward` the backward's."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,11 +40,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
-from ._call import check_ops, launch, lib, ptr, row_stride, rows, workspace
+from ._call import check_ops, cotangent, launch, lib, ptr, row_stride, rows, workspace
 
 HEAD_DIMS = (32, 64)
-MAX_M, MAX_C, MAX_T = _abi.GH_XF_MAX_M, _abi.GH_XF_MAX_C, _abi.GH_XF_MAX_T
-PROLOGUES = {"none": _abi.GH_XF_PRO_NONE, "ln": _abi.GH_XF_PRO_LN, "gn": _abi.GH_XF_PRO_GN}
+MAX_M, MAX_C, MAX_T, GRAD_MAX_M = _abi.GH_XF_MAX_M, _abi.GH_XF_MAX_C, _abi.GH_XF_MAX_T, _abi.GH_XF_GRAD_MAX_M
+GRADS = ("none", "input")
+PROLOGUES = {"none": _abi.GH_XF_PRO_NONE, "ln": _abi.GH_XF_PRO_LN, "gn": _abi.GH_XF_PRO_GN, "cf": _abi.GH_XF_PRO_CF}
 EPILOGUES = {"plain": _abi.GH_XF_EPI_PLAIN, "bias_res": _abi.GH_XF_EPI_BIAS_RES, "geglu": _abi.GH_XF_EPI_GEGLU,
              "bias_res_cf": _abi.GH_XF_EPI_BIAS_RES_CF}
 GN_EPS, LN_EPS = 1e-6, 1e-5
@@ -152,12 +163,12 @@ def group_moments(x: torch.Tensor, groups: int) -> torch.Tensor:
 
 def linear(x, w, *, prologue="none", epilogue="plain", bias=None, gamma=None, beta=None, eps=LN_EPS, moments=None, groups=0, res=None,
            rows_per_batch=0):
-    """One gh_xf_linear call. x: (T, K) rows read in place through their row stride, or under prologue="gn" the channel-first
-    (B, K, N). Returns (T, N_out), or under epilogue="bias_res_cf" the channel-first (B, N_out, N) (res likewise)."""
+    """One gh_xf_linear call. x: (T, K) rows read in place through their row stride, or under prologue="gn" and "cf" the
+    channel-first (B, K, N). dX = dY W is linear(dY, W.t().contiguous()). Returns (T, N_out), or under epilogue="bias_res_cf" the channel-first (B, N_out, N) (res likewise)."""
     pro, epi = PROLOGUES[prologue], EPILOGUES[epilogue]
     a = _abi.GhXfLinear()
     keep = [w.contiguous()]
-    if prologue == "gn":
+    if prologue in ("gn", "cf"):
         if x.shape[2] > 1 and x.stride(2) != 1:
             x = x.contiguous()
         B, K, N = x.shape
@@ -203,13 +214,83 @@ def attention(qkv: torch.Tensor, B: int, N: int, heads: int, D: int) -> torch.Te
     return out
 
 
+# ---- the single launches of the backward ---------------------------------------------------------------------------------------------
+def gelu_grad(g: torch.Tensor) -> torch.Tensor:
+    """gelu'(g) as the kernels state it: 0.5 (1 + erf(g * 0.70710678)) + g * 0.39894228 * exp(-0.5 g^2)."""
+    return 0.5 * (1 + torch.erf(g * 0.70710678)) + g * 0.39894228 * torch.exp(-0.5 * g * g)
+
+
+def attention_lse(qkv: torch.Tensor, B: int, N: int, heads: int, D: int):
+    """`attention` that also returns lse (B, heads, N), the logarithm of each query's sum of exp((q.k) D^-0.5)."""
+    qkv = rows(qkv)
+    out = torch.empty(B * N, heads * D, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(B, heads, N, dtype=torch.float32, device=qkv.device)
+    launch("gh_xf_attention_lse", qkv.device, ptr(qkv), row_stride(qkv), B, N, heads, D, ptr(out), heads * D, ptr(lse),
+           detail=f" (B={B}, N={N}, heads={heads}, D={D})")
+    return out, lse
+
+
+def attention_backward(qkv, out, lse, dout, B: int, N: int, heads: int, D: int, dqkv: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dqkv (B N, 3 heads D) = [dq | dk | dv] for the cotangent dout (B N, heads D) of `attention_lse`'s out; qkv and dout are read
+    in place. dqkv: a buffer to write into (its rows past B N stay as they are)."""
+    qkv, out, dout = rows(qkv), rows(out), rows(dout)
+    if dqkv is None:
+        dqkv = torch.empty(B * N, 3 * heads * D, dtype=torch.float32, device=qkv.device)
+    nbytes = int(lib().gh_xf_attention_backward_workspace_bytes(B, N, heads))
+    ws = workspace(nbytes, qkv.device)
+    launch("gh_xf_attention_backward", qkv.device, ptr(qkv), row_stride(qkv), ptr(out), row_stride(out), ptr(lse.contiguous()), ptr(dout),
+           row_stride(dout), B, N, heads, D, ptr(dqkv), 3 * heads * D, ptr(ws), nbytes, detail=f" (B={B}, N={N}, heads={heads}, D={D})")
+    return dqkv
+
+
+def geglu_backward(g, h, moments, gamma, beta, w1, b1, w2t) -> torch.Tensor:
+    """[da | dg] (T, 8M) of the feed-forward: g (T, M) the cotangent of its output, h (T, M) its input with the LayerNorm's row
+    moments (T, 2) {mean, rstd}, w1 (8M, M), b1 (8M), w2t (4M, M) = W2.t()."""
+    g, h = rows(g), rows(h)
+    T, M = h.shape
+    y = torch.empty(T, 8 * M, dtype=torch.float32, device=h.device)
+    keep = [t.contiguous() for t in (moments, gamma, beta, w1, b1, w2t)]
+    launch("gh_xf_geglu_backward", h.device, ptr(g), row_stride(g), ptr(h), row_stride(h), *[ptr(t) for t in keep], T, M, ptr(y), 8 * M,
+           detail=f" (T={T}, M={M})")
+    return y
+
+
+def layernorm_backward(dn, x, moments, gamma, g) -> torch.Tensor:
+    """g (T, K) += the LayerNorm's backward of dn (T, K) at x (T, K) with row moments (T, 2) {mean, rstd}, in place. Returns g."""
+    dn, x = rows(dn), rows(x)
+    T, K = x.shape
+    if not g.is_contiguous():
+        raise ValueError("layernorm_backward: g is updated in place and must be contiguous")
+    keep = [moments.contiguous(), gamma.contiguous()]
+    launch("gh_xf_layernorm_backward", x.device, ptr(dn), row_stride(dn), ptr(x), row_stride(x), ptr(keep[0]), ptr(keep[1]), T, K, ptr(g), K,
+           detail=f" (T={T}, K={K})")
+    return g
+
+
+def group_norm_backward(dy, x, moments, gamma, dout, groups: int, eps: float = GN_EPS) -> torch.Tensor:
+    """dx (B, C, N) = dout + the GroupNorm's backward of dy at x, with `group_moments`' moments (B, groups, 2)."""
+    dy, x, dout = dy.contiguous(), x.contiguous(), dout.contiguous()
+    B, Cc, N = x.shape
+    dx = torch.empty_like(x)
+    nbytes = int(lib().gh_xf_group_norm_backward_workspace_bytes(B, Cc, N, groups))
+    ws = workspace(nbytes, x.device)
+    keep = [moments.contiguous(), gamma.contiguous()]
+    launch("gh_xf_group_norm_backward", x.device, ptr(dy), ptr(x), ptr(keep[0]), ptr(keep[1]), ptr(dout), ptr(dx), B, Cc, N, groups, float(eps),
+           ptr(ws), nbytes, detail=f" (B={B}, C={Cc}, N={N}, G={groups})")
+    return dx
+
+
 # ---- the whole stack ------------------------------------------------------------------------------------------------------------------
 class _Packed:
     """The parameters as gh_xf_forward reads them: contiguous float32 tensors (kept alive here), the concatenated [Wq; Wk; Wv], and
-    the ctypes structs that point at them."""
+    the ctypes structs that point at them. `transposed()` adds, on first use, what gh_xf_backward reads: the transposed copies of the
+    backward-data products."""
 
     def __init__(self, params):
         self.keep = []
+        self.fields = []                                         # per layer: GhXfLayer's field name -> the tensor it points at
+        self._t = None
+        self._stem_w = [t.detach().contiguous() for t in (params["norm"][0], params["proj_in"][0], params["proj_out"][0])]
         c = self._c
         self.stem = _abi.GhXfStem(*[c(t) for t in (*params["norm"], *params["proj_in"], *params["proj_out"])])
         self.n_layers = len(params["blocks"])
@@ -221,6 +302,8 @@ class _Packed:
                  "ff2_w": b["ff2"][0], "ff2_b": b["ff2"][1]}
             if a2 is not None:
                 f.update(ln2_w=b["norm2"][0], ln2_b=b["norm2"][1], qkv2=torch.cat([a2["q"], a2["k"], a2["v"]], dim=0), o2_w=a2["o_w"], o2_b=a2["o_b"])
+            f = {k: v.detach().contiguous() for k, v in f.items()}
+            self.fields.append(f)
             for name in _abi.XF_LAYER:
                 setattr(self.layers[i], name, c(f[name]) if name in f else None)
         self.groups, self.heads = params["groups"], params["heads"]
@@ -233,6 +316,24 @@ class _Packed:
         self.keep.append(t)
         return t.data_ptr()
 
+    def transposed(self):
+        """(GhXfStemT, GhXfLayerT array) for gh_xf_backward; the copies are made once and kept here."""
+        if self._t is None:
+            tr = lambda w: self._c(w.t())
+            gn_w, in_w, out_w = self._stem_w
+            stem = _abi.GhXfStemT(self._c(gn_w), tr(in_w), tr(out_w))
+            layers = (_abi.GhXfLayerT * max(self.n_layers, 1))()
+            for i, f in enumerate(self.fields):
+                v = {"ln1_w": self._c(f["ln1_w"]), "qkv1_t": tr(f["qkv1"]), "o1_t": tr(f["o1_w"]), "ln3_w": self._c(f["ln3_w"]),
+                     "ln3_b": self._c(f["ln3_b"]), "ff1_w": self._c(f["ff1_w"]), "ff1_b": self._c(f["ff1_b"]), "ff1_t": tr(f["ff1_w"]),
+                     "ff2_t": tr(f["ff2_w"])}
+                if "qkv2" in f:
+                    v.update(ln2_w=self._c(f["ln2_w"]), qkv2_t=tr(f["qkv2"]), o2_t=tr(f["o2_w"]))
+                for name in _abi.XF_LAYER_T:
+                    setattr(layers[i], name, v.get(name))
+            self._t = (stem, layers)
+        return self._t
+
 
 def _run(packed: _Packed, x: torch.Tensor) -> torch.Tensor:
     B, Cc, N = x.shape
@@ -240,15 +341,81 @@ def _run(packed: _Packed, x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
     if B == 0 or N == 0:
         return out
-    dims = _abi.GhXfDims(B, Cc, N, packed.groups, packed.heads, packed.M // packed.heads, packed.n_layers, packed.gn_eps, packed.ln_eps)
+    dims = _dims(packed, x)
     nbytes = int(lib().gh_xf_workspace_bytes(C.byref(dims)))
     ws = workspace(nbytes, x.device)
-    launch("gh_xf_forward", x.device, C.byref(dims), C.byref(packed.stem), packed.layers, ptr(x), ptr(out), ptr(ws), nbytes,
-           detail=f" (B={B}, C={Cc}, N={N}, heads={packed.heads}, D={packed.M // packed.heads}, layers={packed.n_layers})")
+    launch("gh_xf_forward", x.device, C.byref(dims), C.byref(packed.stem), packed.layers, ptr(x), ptr(out), ptr(ws), nbytes, detail=_detail(packed, x))
     return out
 
 
-def _params_reason(params, x) -> Optional[str]:
+def _dims(packed: _Packed, x) -> "_abi.GhXfDims":
+    B, Cc, N = x.shape
+    return _abi.GhXfDims(B, Cc, N, packed.groups, packed.heads, packed.M // packed.heads, packed.n_layers, packed.gn_eps, packed.ln_eps)
+
+
+def _detail(packed: _Packed, x) -> str:
+    B, Cc, N = x.shape
+    return f" (B={B}, C={Cc}, N={N}, heads={packed.heads}, D={packed.M // packed.heads}, layers={packed.n_layers})"
+
+
+def _run_tape(packed: _Packed, x: torch.Tensor):
+    """gh_xf_forward_tape: (out, the tape as a uint8 tensor)."""
+    out = torch.empty_like(x)
+    dims = _dims(packed, x)
+    nbytes, tbytes = int(lib().gh_xf_workspace_bytes(C.byref(dims))), int(lib().gh_xf_tape_bytes(C.byref(dims)))
+    ws, tape = workspace(nbytes, x.device), workspace(tbytes, x.device)
+    launch("gh_xf_forward_tape", x.device, C.byref(dims), C.byref(packed.stem), packed.layers, ptr(x), ptr(out), ptr(tape), tbytes, ptr(ws), nbytes,
+           detail=_detail(packed, x))
+    return out, tape
+
+
+def _run_backward(packed: _Packed, x: torch.Tensor, tape: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
+    dx = torch.empty_like(x)
+    dims = _dims(packed, x)
+    stem, layers = packed.transposed()
+    nbytes = int(lib().gh_xf_backward_workspace_bytes(C.byref(dims)))
+    ws = workspace(nbytes, x.device)
+    launch("gh_xf_backward", x.device, C.byref(dims), C.byref(stem), layers, ptr(x), ptr(tape), ptr(dout), ptr(dx), ptr(ws), nbytes,
+           detail=_detail(packed, x))
+    return dx
+
+
+class _InputGrad(torch.autograd.Function):
+    """The stack with its backward to x: gh_xf_forward_tape, then gh_xf_backward. The weights are constants."""
+
+    @staticmethod
+    def forward(ctx, x, packed):
+        xc = x.detach().contiguous()
+        ctx.packed = packed
+        if xc.shape[0] == 0 or xc.shape[2] == 0:
+            ctx.save_for_backward(xc)
+            return torch.empty_like(xc)
+        out, tape = _run_tape(packed, xc)
+        ctx.save_for_backward(xc, tape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        if len(ctx.saved_tensors) == 1:
+            return torch.zeros_like(ctx.saved_tensors[0]), None
+        xc, tape = ctx.saved_tensors
+        return _run_backward(ctx.packed, xc, tape, cotangent(dout)), None
+
+
+def _go(packed: _Packed, x: torch.Tensor, grad: str) -> torch.Tensor:
+    """The kernels for a call kernel_reason let through: taped where grad="input" has a gradient to carry, else plain."""
+    if grad == "input" and torch.is_grad_enabled() and x.requires_grad:
+        return _InputGrad.apply(x, packed)
+    return _run(packed, x)
+
+
+def _check_grad(grad: str) -> None:
+    if grad not in GRADS:
+        raise ValueError(f"grad must be 'none' or 'input', got {grad!r}")
+
+
+def _params_reason(params, x, grad: str = "none") -> Optional[str]:
     """Why the kernels cannot run these parameters on x, or None."""
     if not (isinstance(x, torch.Tensor) and x.dim() == 3):
         return "x is not a (B, C, N) tensor"
@@ -259,9 +426,16 @@ def _params_reason(params, x) -> Optional[str]:
     ts = _tensors(params)
     if x.dtype != torch.float32 or any(t.dtype != torch.float32 or t.device != x.device for t in ts):
         return "not float32 on one device"
+    taped = False
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in ts)):
-        return "a gradient is wanted"
+        if grad == "none":
+            return "a gradient is wanted"
+        if any(t.requires_grad for t in ts):
+            return "a parameter wants a gradient"
+        taped = True
     M, Cin = params["proj_in"][0].shape
+    if taped and M > GRAD_MAX_M:
+        return "sizes"
     heads = params["heads"]
     if heads < 1 or M % heads != 0 or not sizes_supported(Cin, params["groups"], heads, M // heads) or x.shape[1] != Cin:
         return "sizes"
@@ -345,24 +519,29 @@ def refresh(module) -> None:
     _cache.pop(module, None)
 
 
-def kernel_reason(module_or_params, x, *, encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None) -> Optional[str]:
-    """None where transformer1d runs the kernels for this call, else the first condition that fails."""
+def kernel_reason(module_or_params, x, *, encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None,
+                  grad: str = "none") -> Optional[str]:
+    """None where transformer1d runs the kernels for this call, else the first condition that fails. grad="input": a gradient wanted
+    by x alone is no reason."""
+    _check_grad(grad)
     if encoder_hidden_states is not None or attention_mask is not None or encoder_attention_mask is not None:
         return "encoder_hidden_states or a mask"
     if isinstance(module_or_params, dict):
-        return _params_reason(module_or_params, x)
-    return _module_reason(module_or_params) or _params_reason(params_of(module_or_params), x)
+        return _params_reason(module_or_params, x, grad)
+    return _module_reason(module_or_params) or _params_reason(params_of(module_or_params), x, grad)
 
 
-def transformer1d(module_or_params, x, *, ops: str = "fused", encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None):
+def transformer1d(module_or_params, x, *, ops: str = "fused", grad: str = "none", encoder_hidden_states=None, attention_mask=None,
+                  encoder_attention_mask=None):
     """x (B, C, N) -> (B, C, N): the backbone's forward. ops="fused" runs the kernels where kernel_reason allows and the restatement
-    everywhere else; ops="torch" always the restatement."""
+    everywhere else; ops="torch" always the restatement. grad="input": the kernels also carry the gradient to x."""
     check_ops(ops)
+    _check_grad(grad)
     is_params = isinstance(module_or_params, dict)
     extra = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
-    if ops == "fused" and kernel_reason(module_or_params, x, **extra) is None:
+    if ops == "fused" and kernel_reason(module_or_params, x, grad=grad, **extra) is None:
         params = module_or_params if is_params else params_of(module_or_params)
-        return _run(_Packed(params) if is_params else _packed_of(module_or_params, params), x)
+        return _go(_Packed(params) if is_params else _packed_of(module_or_params, params), x, grad)
     return transformer1d_ref(module_or_params if is_params else params_of(module_or_params), x, **extra)
 
 
@@ -424,8 +603,9 @@ class Transformer1D(nn.Module):
                                                  for _ in range(num_layers)])
         self.proj_out = nn.Linear(inner, in_channels)
 
-    def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None, ops: str = "fused"):
-        return transformer1d(self, hidden_states, ops=ops, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask,
+    def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None, ops: str = "fused",
+                grad: str = "none"):
+        return transformer1d(self, hidden_states, ops=ops, grad=grad, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask,
                              encoder_attention_mask=encoder_attention_mask)
 
 
@@ -433,37 +613,40 @@ class Transformer1D(nn.Module):
 _fused_cls = {}
 
 
-def _new_fused(base):
-    cls = fused_transformer1d_cls(base)
+def _new_fused(base, grad="none"):
+    cls = fused_transformer1d_cls(base, grad)
     return cls.__new__(cls)
 
 
-def fused_transformer1d_cls(base):
+def fused_transformer1d_cls(base, grad: str = "none"):
     """A subclass of the given Transformer1D class whose forward runs the kernels where kernel_reason allows and is the base class's
-    own forward, with the caller's arguments, everywhere else."""
-    if base not in _fused_cls:
+    own forward, with the caller's arguments, everywhere else. grad="input": the kernels also carry the gradient to the input."""
+    _check_grad(grad)
+    if (base, grad) not in _fused_cls:
         def forward(self, hidden_states, encoder_hidden_states=None, timestep=None, modulation_cond=None, class_labels=None,
                     cross_attention_kwargs=None, attention_mask=None, encoder_attention_mask=None):
             # timestep, modulation_cond and class_labels are read by the adaptive norms alone, which kernel_reason refuses: with plain
             # nn.LayerNorm blocks the base class ignores them (TGS._forward passes modulation_cond to both backbones on every call)
             masks = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
-            if not cross_attention_kwargs and kernel_reason(self, hidden_states, **masks) is None:
-                return _run(_packed_of(self, params_of(self)), hidden_states)
+            asks = masks if grad == "none" else dict(masks, grad=grad)
+            if not cross_attention_kwargs and kernel_reason(self, hidden_states, **asks) is None:
+                return _go(_packed_of(self, params_of(self)), hidden_states, grad)
             kw = dict(masks, timestep=timestep, modulation_cond=modulation_cond, class_labels=class_labels, cross_attention_kwargs=cross_attention_kwargs)
             return base.forward(self, hidden_states, **{k: v for k, v in kw.items() if v is not None})
 
         def reduce_ex(self, protocol):
             # the class is made at run time and no module attribute names it: a pickle rebuilds it from its base
-            return _new_fused, (base,), self.__dict__
+            return _new_fused, (base, grad), self.__dict__
 
-        _fused_cls[base] = type(base.__name__, (base,), {"forward": forward, "__reduce_ex__": reduce_ex, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X fused forward"})
-    return _fused_cls[base]
+        doc = f"{base.__module__}.{base.__name__} with the MI355X fused forward" + (" and backward to the input" if grad == "input" else "")
+        _fused_cls[(base, grad)] = type(base.__name__, (base,), {"forward": forward, "__reduce_ex__": reduce_ex, "__module__": __name__,
+                                                                 "__doc__": doc, "_gh_base": base, "_gh_grad": grad})
+    return _fused_cls[(base, grad)]
 
 
-def fuse_transformer1d(module):
+def fuse_transformer1d(module, grad: str = "none"):
     """Swap the module's class for fused_transformer1d_cls of its own class. Module objects, parameters and the state dict are
-    untouched; calling it again changes nothing. Returns the module."""
-    if type(module) not in _fused_cls.values():
-        module.__class__ = fused_transformer1d_cls(type(module))
+    untouched; calling it again with the same grad changes nothing, with another it swaps to that class. Returns the module."""
+    base = type(module)._gh_base if type(module) in _fused_cls.values() else type(module)
+    module.__class__ = fused_transformer1d_cls(base, grad)
     return module

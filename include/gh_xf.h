@@ -1,8 +1,9 @@
 /*
  * gh_xf.h — C-ABI of the Transformer1D backbones' forward for frozen inference: what the reference's two backbones
  * (tgs/models/transformers.py:673-908, called at infer_one_shot.py:256-264) ask of a GroupNorm, about 85 library launches of
- * dense float32 GEMMs, LayerNorms, SDPA and a GEGLU per forward. Forward only: there is no backward here, and the Python layer
- * falls back to torch wherever a gradient is wanted.
+ * dense float32 GEMMs, LayerNorms, SDPA and a GEGLU per forward. The forward serves frozen inference; a second, opt-in path keeps
+ * a tape and backpropagates to the input x alone, every weight frozen (the one-shot fit's identity code reaches the loss through
+ * the texture backbone). Wherever a parameter wants a gradient the Python layer falls back to torch.
  *
  * The module's mathematics, written from transformers.py and the attribute layout of diffusers' Attention (not pinned against
  * a recorded run of the reference):
@@ -16,7 +17,7 @@
  *
  * Entry points.
  *   gh_xf_linear         Y = epilogue(prologue(X) W^T) over T rows, K a multiple of 32, 1 <= N_out <= GH_XF_MAX_N_OUT.
- *                          prologues   NONE; LN (LayerNorm over the row's K columns); GN (GroupNorm from the per-(batch, group)
+ *                          prologues   NONE; CF (the GN read without the norm); LN (LayerNorm over the row's K columns); GN (GroupNorm from the per-(batch, group)
  *                                      moments gh_xf_group_moments wrote, X read channel first: element (t, c) of the rows is
  *                                      x[b * x_stride_b + c * x_stride + n], t = b * rows_per_batch + n).
  *                          epilogues   PLAIN (with [Wq; Wk; Wv] stacked this writes (T, 3M) in one launch); BIAS_RES
@@ -31,7 +32,7 @@
  *   gh_xf_group_moments  mean and sum of squared deviations per (batch, group), two launches.
  *   gh_xf_attention      softmax(q k^T D^-0.5) v per (batch, head), D in {32, 64}: q, k and v are read in place from one
  *                        (T, 3M) buffer (q at column h D, k at M + h D, v at 2M + h D of a row), out is (T, M). No score
- *                        matrix is written and there is no lse output.
+ *                        matrix is written and there is no lse output (gh_xf_attention_lse has one).
  *   gh_xf_forward        the whole stack, enqueued from C++ in one host call: 4 + 11 launches per layer (7 where attn2 is
  *                        absent).
  *
@@ -68,6 +69,42 @@
  *   query's attention of its q and the batch element's K and V alone: not of the row's place in the launch, of B, or of whether
  *   16-byte loads were used.
  *
+ * The backward to x (frozen weights). gh_xf_forward_tape is gh_xf_forward — the same kernels in the same order, `out` bitwise
+ * the same — with the arrays the backward reads written into a caller's tape instead of the workspace, and the attention in
+ * its gh_xf_attention_lse form. gh_xf_backward runs the chain in reverse from one host call: 5 + 13 launches per layer (8 where
+ * attn2 is absent). Sizes are the forward's with M <= 512, because the product dn = [da | dg] W1 has inner width 8M <=
+ * GH_XF_MAX_K; anything larger is GH_ERR_UNSUPPORTED before any launch.
+ *   tape       parts in this order, each starting on 256 bytes (sizes in floats; T = B N, M = heads D):
+ *                the GroupNorm's moments (B, G, 2);
+ *                per layer three slots, laid out whether or not the layer has an attn2 (an absent one stays unwritten):
+ *                  attn1, attn2:  h (T, M) the stream at the sub-block's input | LN moments (T, 2) {mean, rstd} | qkv (T, 3M) |
+ *                                 the attention's output (T, M) | lse (B, heads, N)
+ *                  feed-forward:  h (T, M) | LN moments (T, 2)
+ *              about 11 M T floats a layer. The (T, 8M) pre-activation of the GEGLU is not kept: the backward forms it again.
+ *   data       dX = dY W is gh_xf_linear over a transposed copy of W (Y = X (W^T)^T, EPI_PLAIN): each dX element is one ascending
+ *              fmaf chain over the output-channel index from zero. GhXfStemT and GhXfLayerT hold those copies. PRO_CF reads X
+ *              channel first as PRO_GN does, without a norm (dh = dout_rows W_out reads dout (B, C, N) in place).
+ *   attention  p = expf(s - lse) with s = (q.k) * scale formed exactly as the forward forms it, lse = mm + logf(l) of the forward's
+ *              pair join; delta = dot(dout, out) per (row, head), one ascending fmaf chain over d from 0; ds = (p * (dot(dout, v)
+ *              - delta)) * scale, dot(dout, v) one ascending fmaf chain over d from 0. The key-block kernel: a workgroup owns
+ *              GH_XF_ATTN_BWD_ROWS = 128 keys of one (batch, head), a wave 32, and sweeps the query tiles in ascending order, 64
+ *              queries per LDS stage as two tiles of 32; dv = sum p dout and dk = sum ds q are each one fmaf chain from 0 over
+ *              the queries, inside a tile of 32 in the order 0 4 1 5 2 6 3 7 8 12 ... A query past N contributes exactly 0 (p
+ *              and ds are masked, lse is not consulted). The query-block kernel: a workgroup owns 128 queries, a wave 32, and
+ *              sweeps the key tiles in ascending order the same way; dq = sum ds k. A key past N contributes exactly 0 to dq,
+ *              and its dk and dv rows are not written. Both kinds of workgroup are enqueued by one launch (the key blocks first);
+ *              neither reads what the other writes.
+ *   GEGLU      one kernel, two X slabs (the cotangent gh and LN3(h)) and three accumulators for the same 64 x 64 tile of the 4M
+ *              inner columns: du = gh W2 (from zero, over W2^T), a and g exactly as the forward's GEGLU epilogue forms them
+ *              (from b1). da = du * gelu(g), dg = (du * a) * gelu'(g), gelu'(g) = 0.5 (1 + erff(g * 0.70710678f)) + (g *
+ *              0.39894228f) * expf((-0.5 g) * g). Neither du nor [a | g] is written.
+ *   LayerNorm  one wave per row, w = dn * gamma, xh = (x - mean) * rstd; s1 = sum w and s2 = sum fmaf(w, xh, .) in the forward's
+ *              lane order and butterfly, each divided by K; g += rstd * ((w - s1) - xh * s2), in place.
+ *   GroupNorm  the same two sums per (batch, group): stage one per chunk of GH_XF_GN_CHUNK positions as gh_xf_group_moments
+ *              (thread = position, channels ascending, the butterfly, (s0 + s1) + (s2 + s3)), stage two adds the chunks in
+ *              ascending order; rstd = 1 / sqrtf(m2 / (cpg N) + eps) as the prologue forms it. Then one element-wise channel-first
+ *              pass: dx = dout + rstd * ((w - s1 / (cpg N)) - xh * (s2 / (cpg N))); the + dout is the residual + x of the output.
+ *
  * Conventions are those of gh_pool.h: caller-allocated buffers, all work enqueued on `hip_stream`, no host synchronisation, no
  * allocation, nothing thrown, HIP-graph capturable; GhStatus return codes, returned before any launch for bad arguments or a
  * short workspace. Strides are in float elements. All pointers 4-byte aligned, a workspace 16-byte aligned. An input whose
@@ -93,10 +130,14 @@ extern "C" {
 #define GH_XF_MAX_K 4096   /* 4 GH_XF_MAX_M: the feed-forward's inner width */
 #define GH_XF_MAX_N_OUT 8192 /* the widest output of gh_xf_linear: 8 GH_XF_MAX_M */
 #define GH_XF_MAX_T (1 << 30)
+#define GH_XF_ATTN_BWD_ROWS 128 /* queries (dq) or keys (dk, dv) per workgroup of the attention's backward: 32 per wave */
+#define GH_XF_ATTN_BWD_STAGE 64 /* rows of the swept operand per LDS stage of the attention's backward */
+#define GH_XF_GRAD_MAX_M 512    /* the backward to x: 8 M <= GH_XF_MAX_K */
 
 #define GH_XF_PRO_NONE 0
 #define GH_XF_PRO_LN 1
 #define GH_XF_PRO_GN 2
+#define GH_XF_PRO_CF 3     /* X channel first as under PRO_GN, no norm: x_stride, x_stride_b and rows_per_batch as there */
 
 #define GH_XF_EPI_PLAIN 0
 #define GH_XF_EPI_BIAS_RES 1
@@ -162,6 +203,68 @@ int gh_xf_attention(const float* qkv, int64_t qkv_stride, int B, int N, int head
 size_t gh_xf_workspace_bytes(const GhXfDims* dims);
 int gh_xf_forward(const GhXfDims* dims, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out,
                   void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* ---- the backward to x, every weight frozen ---- */
+
+/* What the backward reads of the frozen weights: transposed copies for the backward-data products, the norms' scales, and the
+ * feed-forward's first layer as the forward reads it (the GEGLU's pre-activation is formed again). */
+typedef struct GhXfStemT {
+  const float* gn_w;          /* C */
+  const float* in_t;          /* (C, M): proj_in's weight transposed */
+  const float* out_t;         /* (M, C): proj_out's weight transposed */
+} GhXfStemT;
+
+typedef struct GhXfLayerT {
+  const float* ln1_w;         /* M */
+  const float* qkv1_t;        /* (M, 3M): [Wq; Wk; Wv] of attn1 transposed */
+  const float* o1_t;          /* (M, M): to_out[0]'s weight transposed */
+  const float* ln2_w;
+  const float* qkv2_t;        /* NULL where the block has no attn2: ln2_w and o2_t are then ignored */
+  const float* o2_t;
+  const float *ln3_w, *ln3_b; /* M */
+  const float *ff1_w, *ff1_b; /* (8M, M), 8M: as GhXfLayer's */
+  const float* ff1_t;         /* (M, 8M): ff1_w transposed */
+  const float* ff2_t;         /* (4M, M): ff2_w transposed */
+} GhXfLayerT;
+
+/* gh_xf_attention that also writes lse (B, heads, N) = mm + logf(l) of the pair join; out is bitwise gh_xf_attention's. */
+int gh_xf_attention_lse(const float* qkv, int64_t qkv_stride, int B, int N, int heads, int D, float* out, int64_t out_stride,
+                        float* lse, void* hip_stream);
+
+/* dqkv (B N, 3 heads D) with row stride dqkv_stride: [dq | dk | dv] in the columns of qkv, every element written. out and dout are
+ * (B N, heads D) rows, lse (B, heads, N) contiguous. The workspace holds delta, one float per (batch, head, row). */
+size_t gh_xf_attention_backward_workspace_bytes(int B, int N, int heads);
+int gh_xf_attention_backward(const float* qkv, int64_t qkv_stride, const float* out, int64_t out_stride, const float* lse,
+                             const float* dout, int64_t dout_stride, int B, int N, int heads, int D, float* dqkv,
+                             int64_t dqkv_stride, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* y (T, 8M) = [da | dg] of the feed-forward: g (T, M) the cotangent of its output, h (T, M) its input with the LayerNorm's row
+ * moments (T, 2) {mean, rstd}, gamma and beta (M), w1 (8M, M), b1 (8M), w2t (4M, M) = W2 transposed. M a multiple of 32. */
+int gh_xf_geglu_backward(const float* g, int64_t g_stride, const float* h, int64_t h_stride, const float* moments,
+                         const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2t, int T, int M,
+                         float* y, int64_t y_stride, void* hip_stream);
+
+/* g (T, K) += the LayerNorm's backward of dn (T, K) at x (T, K) with moments (T, 2) {mean, rstd}; any K >= 1. */
+int gh_xf_layernorm_backward(const float* dn, int64_t dn_stride, const float* x, int64_t x_stride, const float* moments,
+                             const float* gamma, int T, int K, float* g, int64_t g_stride, void* hip_stream);
+
+/* dx = dout + the GroupNorm's backward of dy at x; dy, x, dout, dx (B, C, N) contiguous, moments (B, G, 2) {mean, m2} of
+ * gh_xf_group_moments. dx may not alias dy, x or dout. */
+size_t gh_xf_group_norm_backward_workspace_bytes(int B, int C, int N, int G);
+int gh_xf_group_norm_backward(const float* dy, const float* x, const float* moments, const float* gamma, const float* dout,
+                              float* dx, int B, int C, int N, int G, float eps, void* workspace, size_t ws_bytes,
+                              void* hip_stream);
+
+/* gh_xf_forward that keeps the tape (layout above); workspace as gh_xf_workspace_bytes. 0 bytes for unsupported or empty sizes. */
+size_t gh_xf_tape_bytes(const GhXfDims* dims);
+int gh_xf_forward_tape(const GhXfDims* dims, const GhXfStem* stem, const GhXfLayer* layers, const float* x, float* out,
+                       void* tape, size_t tape_bytes, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* dx (B, C, N) = the gradient of sum(out * dout) with respect to x, from the tape gh_xf_forward_tape wrote for the same dims, x
+ * and weights. x, dout, dx contiguous; dx may not alias x or dout. layers: dims->layers structs in host memory. */
+size_t gh_xf_backward_workspace_bytes(const GhXfDims* dims);
+int gh_xf_backward(const GhXfDims* dims, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape,
+                   const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
