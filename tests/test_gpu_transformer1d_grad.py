@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from tests import transformer1d_cases as K
 from tests.fit_cases import bits, three_way
+from tests.transformer1d_cases import attention_grads, geglu_ref, gn_ref, ln_ref, lse_ref      # shared with the edge tests
 
 pytestmark = pytest.mark.gpu
 
@@ -113,12 +114,6 @@ def make_qkv(dev, B, N, heads, D, seed=0):
     return (torch.randn(B * N, 3 * heads * D, generator=gen) * torch.tensor([2.0, 1.0, 1.0]).repeat_interleave(heads * D)).to(dev)
 
 
-def lse_ref(qkv, B, N, heads, D, dtype):
-    M = heads * D
-    q, k, _v = (t.reshape(B, N, heads, D).transpose(1, 2) for t in qkv.to(dtype).split(M, dim=1))
-    return torch.logsumexp(q @ k.transpose(-1, -2) * D ** -0.5, dim=-1)
-
-
 @pytest.mark.parametrize("N", [1, 33, 64, 129, 257])
 @pytest.mark.parametrize("D,heads", [(32, 2), (64, 1)])
 def test_lse(dev, X, D, heads, N):
@@ -130,13 +125,6 @@ def test_lse(dev, X, D, heads, N):
 
 
 # ---- gh_xf_attention_backward -------------------------------------------------------------------------------------------------------------
-def attention_grads(qkv, dout, B, N, heads, D, dtype):
-    t = qkv.to(dtype).requires_grad_(True)
-    g, = torch.autograd.grad(K.attention_ref(t, B, N, heads, D, dtype), t, dout.to(dtype))
-    M = heads * D
-    return {"dq": g[:, :M], "dk": g[:, M:2 * M], "dv": g[:, 2 * M:]}
-
-
 def attention_kernel(X, qkv, dout, B, N, heads, D, dqkv=None):
     out, lse = X.attention_lse(qkv, B, N, heads, D)
     return X.attention_backward(qkv, out, lse, dout, B, N, heads, D, dqkv=dqkv)
@@ -196,12 +184,6 @@ def ln_case(dev, T, Kc, seed=0):
     return x, dn, g0, gamma, beta, mom
 
 
-def ln_ref(x, dn, g0, gamma, beta, dtype):
-    t = x.to(dtype).requires_grad_(True)
-    g, = torch.autograd.grad(F.layer_norm(t, (t.shape[1],), gamma.to(dtype), beta.to(dtype), 1e-5), t, dn.to(dtype))
-    return {"g": g0.to(dtype) + g}
-
-
 @pytest.mark.parametrize("T", [1, 63, 64, 65, 257])
 @pytest.mark.parametrize("Kc", [32, 64, 512])
 def test_layernorm_backward(dev, X, Kc, T):
@@ -233,14 +215,6 @@ def geglu_case(dev, T, M, seed=0, wide_gate=False):
     return d
 
 
-def geglu_ref(d, dtype):
-    t = {k: v.to(dtype) for k, v in d.items()}
-    pre = F.linear(F.layer_norm(t["h"], (t["h"].shape[1],), t["gamma"], t["beta"], 1e-5), t["w1"], t["b1"]).detach().requires_grad_(True)
-    a, g = pre.chunk(2, dim=-1)
-    y, = torch.autograd.grad(F.linear(a * F.gelu(g), t["w2"]), pre, t["g"])
-    return {"dadg": y, "gate": pre.detach()[:, pre.shape[1] // 2:]}
-
-
 @pytest.mark.parametrize("T", [1, 63, 65, 129])
 @pytest.mark.parametrize("M", [32, 64])
 def test_geglu_backward(dev, X, M, T):
@@ -260,12 +234,6 @@ def test_geglu_backward_both_tails_of_the_gelu_derivative(dev, X):
 
 
 # ---- gh_xf_group_norm_backward --------------------------------------------------------------------------------------------------------------
-def gn_ref(x, dy, dout, gamma, beta, G, dtype):
-    t = x.to(dtype).requires_grad_(True)
-    g, = torch.autograd.grad(F.group_norm(t, G, gamma.to(dtype), beta.to(dtype), 1e-6), t, dy.to(dtype))
-    return {"dx": dout.to(dtype) + g}
-
-
 @pytest.mark.parametrize("N", [1, 33, 2 * K.GN_CHUNK + 1])
 @pytest.mark.parametrize("Cc", [32, 64])
 def test_group_norm_backward(dev, X, Cc, N):

@@ -20,7 +20,7 @@ LINEAR_T = (1, 31, 33, 63, 64, 65, 129, 257)
 LINEAR_SHAPES = [(T, 64, COL_TILE + 1) for T in LINEAR_T] + [(65, 32, COL_TILE - 1), (129, 512, COL_TILE), (257, 512, 2 * COL_TILE + 2), (33, 32, 1)]
 PROLOGUES = ("none", "ln", "gn")
 EPILOGUES = ("plain", "bias_res", "geglu", "bias_res_cf")
-ATTN_N = (1, 31, 32, 33, 127, 128, 129, 257)
+ATTN_N = (1, 31, 32, 33, 63, 64, 65, 97, 127, 128, 129, 257)    # 63 .. 65: the stage of 64 keys and the tile of 64 queries; 97: one key in the odd wave's tile
 # (C, heads, D, layers, B, N, attn2)
 STACKS = [(64, 1, 64, 2, 2, 129, True), (64, 2, 32, 10, 1, 129, True), (512, 8, 64, 1, 2, 257, True), (64, 2, 32, 2, 2, 65, False)]
 
@@ -193,6 +193,40 @@ def attention_ref(qkv, B, N, heads, D, dtype):
     q, k, v = (t.reshape(B, N, heads, D).transpose(1, 2) for t in qkv.to(dtype).split(M, dim=1))
     s = q @ k.transpose(-1, -2) * D ** -0.5
     return (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(B * N, M)
+
+
+# ---- references of the backward's single launches: torch's autograd in `dtype` ----------------------------------------------------------
+def lse_ref(qkv, B, N, heads, D, dtype):
+    M = heads * D
+    q, k, _v = (t.reshape(B, N, heads, D).transpose(1, 2) for t in qkv.to(dtype).split(M, dim=1))
+    return torch.logsumexp(q @ k.transpose(-1, -2) * D ** -0.5, dim=-1)
+
+
+def attention_grads(qkv, dout, B, N, heads, D, dtype):
+    t = qkv.to(dtype).requires_grad_(True)
+    g, = torch.autograd.grad(attention_ref(t, B, N, heads, D, dtype), t, dout.to(dtype))
+    M = heads * D
+    return {"dq": g[:, :M], "dk": g[:, M:2 * M], "dv": g[:, 2 * M:]}
+
+
+def ln_ref(x, dn, g0, gamma, beta, dtype):
+    t = x.to(dtype).requires_grad_(True)
+    g, = torch.autograd.grad(F.layer_norm(t, (t.shape[1],), gamma.to(dtype), beta.to(dtype), 1e-5), t, dn.to(dtype))
+    return {"g": g0.to(dtype) + g}
+
+
+def geglu_ref(d, dtype):
+    t = {k: v.to(dtype) for k, v in d.items()}
+    pre = F.linear(F.layer_norm(t["h"], (t["h"].shape[1],), t["gamma"], t["beta"], 1e-5), t["w1"], t["b1"]).detach().requires_grad_(True)
+    a, g = pre.chunk(2, dim=-1)
+    y, = torch.autograd.grad(F.linear(a * F.gelu(g), t["w2"]), pre, t["g"])
+    return {"dadg": y, "gate": pre.detach()[:, pre.shape[1] // 2:]}
+
+
+def gn_ref(x, dy, dout, gamma, beta, G, dtype):
+    t = x.to(dtype).requires_grad_(True)
+    g, = torch.autograd.grad(F.group_norm(t, G, gamma.to(dtype), beta.to(dtype), 1e-6), t, dy.to(dtype))
+    return {"dx": dout.to(dtype) + g}
 
 
 def strided_misaligned(t, pad=5):
