@@ -665,12 +665,58 @@ def declare_xf(lib: C.CDLL) -> None:
     lib.gh_xf_backward.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStemT), C.POINTER(GhXfLayerT), V, V, V, V, V, C.c_size_t, V]
 
 
+# ---- include/gh_lpips.h: the evaluator's perceptual score, LPIPS over AlexNet (a header of its own, as gh_conv.h is) ----
+GH_LPIPS_RELU = 1
+GH_LPIPS_MAX_C = 512
+GH_LPIPS_PIXELS = 128
+GH_LPIPS_CHUNK = 128
+GH_LPIPS_FILL = 512
+GH_LPIPS_FLAT_CIN = 16
+GH_LPIPS_HEAD_PIXELS = 256
+GH_LPIPS_TAPS = 5
+GH_LPIPS_MIN_SIZE = 31
+GH_LPIPS_PRED_HWC = 1
+GH_LPIPS_GT_HWC = 2
+GH_LPIPS_QUANTIZE = 4
+GH_LPIPS_SIGNED = 8
+
+LPIPS_SYMBOLS = ("gh_conv2d_weight_floats", "gh_conv2d_forward", "gh_maxpool3x3s2_forward", "gh_lpips_layer_workspace", "gh_lpips_layer",
+                 "gh_lpips_prepare", "gh_lpips_workspace", "gh_lpips_forward")
+
+
+class GhLpipsWeights(C.Structure):
+    """The frozen parameters of gh_lpips_forward: fifteen pointers in the header's order."""
+    _fields_ = [("w", C.c_void_p * GH_LPIPS_TAPS), ("b", C.c_void_p * GH_LPIPS_TAPS), ("lin", C.c_void_p * GH_LPIPS_TAPS)]
+
+
+def declare_lpips(lib: C.CDLL) -> None:
+    """Attach argtypes/restypes for every symbol include/gh_lpips.h declares."""
+    V, I, U, L = C.c_void_p, C.c_int, C.c_uint32, C.c_longlong
+    lib.gh_conv2d_weight_floats.restype = C.c_size_t
+    lib.gh_conv2d_weight_floats.argtypes = [I, I, I]
+    lib.gh_conv2d_forward.restype = C.c_int
+    lib.gh_conv2d_forward.argtypes = [V, I, I, I, I, I, I, I, I, V, V, U, I, V, V]
+    lib.gh_maxpool3x3s2_forward.restype = C.c_int
+    lib.gh_maxpool3x3s2_forward.argtypes = [V, I, I, I, I, V, V]
+    lib.gh_lpips_layer_workspace.restype = C.c_size_t
+    lib.gh_lpips_layer_workspace.argtypes = [I, L]
+    lib.gh_lpips_layer.restype = C.c_int
+    lib.gh_lpips_layer.argtypes = [V, I, L, I, V, I, V, V, V, C.c_size_t, V]
+    lib.gh_lpips_prepare.restype = C.c_int
+    lib.gh_lpips_prepare.argtypes = [V, V, V, V, I, I, I, I, I, U, V, V, V, V]
+    lib.gh_lpips_workspace.restype = C.c_size_t
+    lib.gh_lpips_workspace.argtypes = [I, I, I, C.POINTER(I)]
+    lib.gh_lpips_forward.restype = C.c_int
+    lib.gh_lpips_forward.argtypes = [V, I, I, I, C.POINTER(I), C.POINTER(GhLpipsWeights), V, V, V, C.c_size_t, V]
+
+
 ALL_SYMBOLS = (EXPORTED_SYMBOLS + METRICS_SYMBOLS + POOL_SYMBOLS + HEAD_SYMBOLS + VERT_SYMBOLS + PLANE_SYMBOLS + ATTN_SYMBOLS + UVD_SYMBOLS +
-               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS + MANO_SYMBOLS + XF_SYMBOLS)
+               COND_SYMBOLS + RES_SYMBOLS + ATTN_ROWS_SYMBOLS + SCENE_SYMBOLS + TRUNK_SYMBOLS + CONV_SYMBOLS + MANO_SYMBOLS + XF_SYMBOLS +
+               LPIPS_SYMBOLS)
 
 
 def declare(lib: C.CDLL) -> None:
-    """Attach argtypes/restypes for every symbol of the sixteen headers (ALL_SYMBOLS)."""
+    """Attach argtypes/restypes for every symbol of the seventeen headers (ALL_SYMBOLS)."""
     for one in (declare_raster, declare_metrics, declare_pool, declare_head, declare_vert, declare_plane, declare_attn, declare_uvd, declare_cond, declare_res,
-                declare_attn_rows, declare_scene, declare_trunk, declare_conv, declare_mano, declare_xf):
+                declare_attn_rows, declare_scene, declare_trunk, declare_conv, declare_mano, declare_xf, declare_lpips):
         one(lib)

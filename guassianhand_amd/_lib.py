@@ -27,7 +27,7 @@ SOURCES = ("gh_api.hip", "gh_preprocess.hip", "gh_binning.hip", "gh_render.hip",
            os.path.join("..", "csrc_res", "gh_res.hip"), os.path.join("..", "csrc_attn_rows", "gh_attn_rows.hip"),
            os.path.join("..", "csrc_scene", "gh_scene.hip"), os.path.join("..", "csrc_trunk", "gh_trunk.hip"),
            os.path.join("..", "csrc_conv", "gh_conv.hip"), os.path.join("..", "csrc_mano", "gh_mano.hip"),
-           os.path.join("..", "csrc_xf", "gh_xf.hip"))
+           os.path.join("..", "csrc_xf", "gh_xf.hip"), os.path.join("..", "csrc_lpips", "gh_lpips.hip"))
 HEADERS = ("gh_internal.h", os.path.join("..", "..", "include", "gh_raster.h"), os.path.join("..", "..", "include", "gh_metrics.h"),
            os.path.join("..", "..", "include", "gh_pool.h"), os.path.join("..", "..", "include", "gh_head.h"),
            os.path.join("..", "..", "include", "gh_vert.h"), os.path.join("..", "..", "include", "gh_plane.h"),
@@ -36,6 +36,7 @@ HEADERS = ("gh_internal.h", os.path.join("..", "..", "include", "gh_raster.h"), 
            os.path.join("..", "..", "include", "gh_attn_rows.h"), os.path.join("..", "..", "include", "gh_scene.h"),
            os.path.join("..", "..", "include", "gh_trunk.h"), os.path.join("..", "..", "include", "gh_conv.h"),
            os.path.join("..", "..", "include", "gh_mano.h"), os.path.join("..", "..", "include", "gh_xf.h"),
+           os.path.join("..", "..", "include", "gh_lpips.h"),
            os.path.join("..", "csrc_rows", "gh_rows.h"), os.path.join("..", "csrc_head", "gh_head_act.h"))
 # -ffp-contract=off: FMAs only where the source says fmaf() (arithmetic contract)
 # -fno-slp-vectorize: keeps the DPP butterflies as v_add_f32_dpp instead of v_mov_dpp + v_pk_add_f32

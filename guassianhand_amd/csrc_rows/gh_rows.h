@@ -22,6 +22,8 @@
 //             template's tile count.
 // gh_pool.hip and gh_metrics.hip take ghr_align from here; gh_attn.hip takes ghr_stage. csrc_attn_rows/gh_attn_rows.hip takes the tile,
 // the layers and ghr_allow_lds, and gathers its rows through a list (ghr_stage_rows). ghr_al4 is every block's test of a float pointer.
+// csrc_conv/gh_conv.hip and csrc_lpips/gh_lpips.hip take the slabs (ghr_fetch_in, ghr_put, GHR_WP) and the accumulator map for their
+// own convolution products, whose operand gather is theirs.
 #ifndef GH_ROWS_H
 #define GH_ROWS_H
 

@@ -10,7 +10,8 @@ include/gh_metrics.h). Per view, with images in [0,1]:
    float image from its dtype, (-1, 1)), averaged over the pixels whose window lies inside the crop, then over the channels.
    NaN when the crop is smaller than 7 in either direction (skimage raises ValueError there; so does Evaluator.compute_score).
 
-LPIPS and the reference's PNG dumps of the crops are not computed. CPU tensors go through `_image_scores_cpu`, a plain float64
+LPIPS is the fourth number of the reference's evaluator and lives in lpips.py (`lpips_scores`; Evaluator(lpips=net) adds it); the
+reference's PNG dumps of the crops are not written. CPU tensors go through `_image_scores_cpu`, a plain float64
 torch restatement of the same four steps (the yardstick of the GPU tests); ROCm tensors go through the HIP kernels only."""
 from __future__ import annotations
 
@@ -135,12 +136,14 @@ def _image_scores_cpu(pred, gt, mbox, bbm, layout: str, R: float) -> ImageScores
 
 # ---- drop-in for the reference's evaluator.Evaluator ------------------------------------------------------------------------
 class Evaluator:
-    """`evaluator.Evaluator` without LPIPS and without the PNG dumps: compute_score returns {'mse', 'psnr', 'ssim'} as Python floats
-    from one device-to-host copy. `result_dir` is kept for the reference's test_step, which sets it, and is not used."""
+    """`evaluator.Evaluator` without the PNG dumps: compute_score returns {'mse', 'psnr', 'ssim'} as Python floats from one
+    device-to-host copy, and with `lpips` (a lpips.AlexLPIPS holding the weights) also 'lpips', the reference's fourth number, from a
+    second one. `result_dir` is kept for the reference's test_step, which sets it, and is not used."""
 
-    def __init__(self, data_range: float = 2.0):
+    def __init__(self, data_range: float = 2.0, lpips=None):
         self.result_dir = None
         self.data_range = data_range
+        self.lpips = lpips
 
     def compute_score(self, rgb_pred, rgb_gt, input_imgs=None, mask_at_box=None, human_idx=None, frame_index=None, view_index=None,
                       **ignored):
@@ -158,4 +161,12 @@ class Evaluator:
         if w < 7 or h < 7:
             raise ValueError(f"SSIM needs a crop of at least 7x7 pixels; mask_at_box's bounding box is {w}x{h} "
                              "(skimage's structural_similarity raises here too)")
-        return {"mse": float(host[0]), "psnr": float(host[1]), "ssim": float(host[2])}
+        out = {"mse": float(host[0]), "psnr": float(host[1]), "ssim": float(host[2])}
+        if self.lpips is not None:
+            from .lpips import MIN_SIZE, _scores_with_boxes
+            if w < MIN_SIZE or h < MIN_SIZE:
+                raise ValueError(f"LPIPS needs a crop of at least {MIN_SIZE}x{MIN_SIZE} pixels (AlexNet's smallest input); "
+                                 f"mask_at_box's bounding box is {w}x{h}")
+            box = (int(host[3]), int(host[4]), w, h)
+            out["lpips"] = float(_scores_with_boxes(self.lpips, pred, gt, s.bbox, [box], None, "chw", True, "fused")[0])
+        return out
