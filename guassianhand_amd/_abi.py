@@ -582,13 +582,20 @@ GH_XF_MAX_T = 1 << 30
 GH_XF_ATTN_BWD_ROWS = 128
 GH_XF_ATTN_BWD_STAGE = 64
 GH_XF_GRAD_MAX_M = 512
+GH_XF_WGRAD_ROWS = 32
+GH_XF_WGRAD_CHUNK = 256
+GH_XF_WGRAD_MAX_BLOCKS = 1024
+GH_XF_LNP_ROWS = 64
 GH_XF_PRO_NONE, GH_XF_PRO_LN, GH_XF_PRO_GN, GH_XF_PRO_CF = 0, 1, 2, 3
 GH_XF_EPI_PLAIN, GH_XF_EPI_BIAS_RES, GH_XF_EPI_GEGLU, GH_XF_EPI_BIAS_RES_CF = 0, 1, 2, 3
 
 XF_SYMBOLS = ("gh_xf_linear_workspace_bytes", "gh_xf_linear", "gh_xf_group_moments_workspace_bytes", "gh_xf_group_moments", "gh_xf_attention",
               "gh_xf_workspace_bytes", "gh_xf_forward", "gh_xf_attention_lse", "gh_xf_attention_backward_workspace_bytes",
               "gh_xf_attention_backward", "gh_xf_geglu_backward", "gh_xf_layernorm_backward", "gh_xf_group_norm_backward_workspace_bytes",
-              "gh_xf_group_norm_backward", "gh_xf_tape_bytes", "gh_xf_forward_tape", "gh_xf_backward_workspace_bytes", "gh_xf_backward")
+              "gh_xf_group_norm_backward", "gh_xf_tape_bytes", "gh_xf_forward_tape", "gh_xf_backward_workspace_bytes", "gh_xf_backward",
+              "gh_xf_linear_wgrad_chunk", "gh_xf_linear_wgrad_workspace_bytes", "gh_xf_linear_wgrad", "gh_xf_layernorm_param_grads_workspace_bytes",
+              "gh_xf_layernorm_param_grads", "gh_xf_group_norm_param_grads_workspace_bytes", "gh_xf_group_norm_param_grads",
+              "gh_xf_backward_params_workspace_bytes", "gh_xf_backward_params")
 XF_STEM = ("gn_w", "gn_b", "in_w", "in_b", "out_w", "out_b")
 XF_STEM_T = ("gn_w", "in_t", "out_t")
 XF_LAYER_T = ("ln1_w", "qkv1_t", "o1_t", "ln2_w", "qkv2_t", "o2_t", "ln3_w", "ln3_b", "ff1_w", "ff1_b", "ff1_t", "ff2_t")
@@ -622,6 +629,22 @@ class GhXfStemT(C.Structure):
 
 class GhXfLayerT(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in XF_LAYER_T]
+
+
+class GhXfWgrad(C.Structure):
+    _fields_ = [("T", C.c_int32), ("K", C.c_int32), ("N_out", C.c_int32), ("prologue", C.c_int32), ("dy_cf", C.c_int32),
+                ("rows_per_batch", C.c_int32), ("groups", C.c_int32), ("eps", C.c_float),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("x_stride_b", C.c_int64),
+                ("dy", C.c_void_p), ("dy_stride", C.c_int64), ("dy_stride_b", C.c_int64),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("moments", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p)]
+
+
+class GhXfStemG(C.Structure):                                    # the gradients' buffers: GhXfStem's and GhXfLayer's fields
+    _fields_ = [(n, C.c_void_p) for n in XF_STEM]
+
+
+class GhXfLayerG(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in XF_LAYER]
 
 
 def declare_xf(lib: C.CDLL) -> None:
@@ -663,6 +686,25 @@ def declare_xf(lib: C.CDLL) -> None:
     lib.gh_xf_backward_workspace_bytes.argtypes = [C.POINTER(GhXfDims)]
     lib.gh_xf_backward.restype = C.c_int
     lib.gh_xf_backward.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStemT), C.POINTER(GhXfLayerT), V, V, V, V, V, C.c_size_t, V]
+    lib.gh_xf_linear_wgrad_chunk.restype = C.c_int
+    lib.gh_xf_linear_wgrad_chunk.argtypes = [I, I, I]
+    lib.gh_xf_linear_wgrad_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_linear_wgrad_workspace_bytes.argtypes = [I, I, I]
+    lib.gh_xf_linear_wgrad.restype = C.c_int
+    lib.gh_xf_linear_wgrad.argtypes = [C.POINTER(GhXfWgrad), V, C.c_size_t, V]
+    lib.gh_xf_layernorm_param_grads_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_layernorm_param_grads_workspace_bytes.argtypes = [I, I]
+    lib.gh_xf_layernorm_param_grads.restype = C.c_int
+    lib.gh_xf_layernorm_param_grads.argtypes = [V, L, V, L, V, I, I, V, V, V, C.c_size_t, V]
+    lib.gh_xf_group_norm_param_grads_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_group_norm_param_grads_workspace_bytes.argtypes = [I, I, I, I]
+    lib.gh_xf_group_norm_param_grads.restype = C.c_int
+    lib.gh_xf_group_norm_param_grads.argtypes = [V, V, V, I, I, I, I, C.c_float, V, V, V, C.c_size_t, V]
+    lib.gh_xf_backward_params_workspace_bytes.restype = C.c_size_t
+    lib.gh_xf_backward_params_workspace_bytes.argtypes = [C.POINTER(GhXfDims)]
+    lib.gh_xf_backward_params.restype = C.c_int
+    lib.gh_xf_backward_params.argtypes = [C.POINTER(GhXfDims), C.POINTER(GhXfStemT), C.POINTER(GhXfLayerT), C.POINTER(GhXfStem), C.POINTER(GhXfLayer),
+                                          C.POINTER(GhXfStemG), C.POINTER(GhXfLayerG), V, V, V, V, V, C.c_size_t, V]
 
 
 # ---- include/gh_lpips.h: the evaluator's perceptual score, LPIPS over AlexNet (a header of its own, as gh_conv.h is) ----

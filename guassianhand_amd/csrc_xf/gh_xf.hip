@@ -1,8 +1,9 @@
 // gh_xf.hip — the Transformer1D backbones' forward (include/gh_xf.h): the LDS-tiled product with its prologues and epilogues, the
 // LayerNorm and GroupNorm moments, the streaming-softmax attention for D = 32 and 64, and the host loop that enqueues a whole
 // backbone; behind them the backward to the input for frozen weights (the taped forward is the same host loop with other pointers;
-// the attention's, the GEGLU's and the norms' backward kernels, the host loop in reverse). Exact float32 MFMA, no atomics, no workgroup
-// that waits for another.
+// the attention's, the GEGLU's and the norms' backward kernels, the host loop in reverse), and behind that the parameters' gradients
+// (the backward-weight product with its join, the norms' two-stage column sums; the same host loop enqueues them beside each step).
+// Exact float32 MFMA, no atomics, no workgroup that waits for another.
 //
 // The product shape is gh_rows.h's "columns" turned round: v_mfma_f32_32x32x2_f32 with the ROW of X as the A operand's i and the
 // output channel as the B operand's j, so that lane l holds channel j = l & 31 of the rows ghr_acc_row(r, l >> 5) and a register's
@@ -1273,6 +1274,374 @@ extern "C" int gh_xf_group_norm_backward(const float* dy, const float* x, const 
   return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
 }
 
+// ==== the parameters' gradients (include/gh_xf.h) ========================================================================================
+#define GW_TS GH_XF_WGRAD_ROWS     // rows of dY and of X per slab
+#define GW_P 65                    // LDS pitch of a slab's 64 columns: odd, so that lane = row writes without a bank conflict
+
+static_assert(GW_TS == 32 && GH_XF_WGRAD_CHUNK % GW_TS == 0, "GhrSlab<2, 16> is 32 rows x 64 columns; a chunk is whole slabs");
+
+// One operand slab (32 rows x 64 columns) on its way into LDS. Rows: gh_rows.h's window, thread i moves rows i / 16 and (i + 256) / 16.
+// Channel first: thread i owns slab row i & 31 and the columns (i >> 5) + 8 it.
+struct GxWSlab {
+  GhrSlab<2, 16> w;
+  float g[8];
+};
+
+template <bool CF>
+__device__ __forceinline__ void gx_wfetch(GxWSlab& t, const float* __restrict__ p, long long stride, long long stride_b, int N, int t0, int t_hi,
+                                          int c0, int ncols, int vec, int tid) {
+  if constexpr (CF) {
+    const int tt = t0 + (tid & 31);
+    const bool live = tt < t_hi;
+    const int b = live ? tt / N : 0, n = live ? tt - b * N : 0;
+    const long long base = (long long)b * stride_b + n;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int c = c0 + (tid >> 5) + 8 * it;
+      t.g[it] = live && c < ncols ? p[base + (long long)c * stride] : 0.f;
+    }
+  } else {
+    ghr_fetch_in(t.w, p, stride, t0, c0, t_hi, ncols, vec, tid);
+  }
+}
+
+template <bool CF>
+__device__ __forceinline__ void gx_wput(const GxWSlab& t, float* s, int tid) {
+  if constexpr (CF) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) s[(tid & 31) * GW_P + (tid >> 5) + 8 * it] = t.g[it];
+  } else {
+    ghr_put(t.w, s, GW_P, tid);
+  }
+}
+
+// X's slab through the prologue into LDS, each element formed as gx_put_x forms it; a row past t_hi or a column past K is zero
+template <int PRO>
+__device__ __forceinline__ void gx_wput_x(const GxWSlab& t, float* s, const GhXfWgrad& a, int t0, int t_hi, int k0, const float (&ln)[2][2], int tid) {
+  if constexpr (PRO == GH_XF_PRO_GN) {
+    const int tt = t0 + (tid & 31), N = a.rows_per_batch, cpg = a.K / a.groups;
+    const bool live = tt < t_hi;
+    const float* mom = a.moments + 2 * (long long)(live ? tt / N : 0) * a.groups;
+    const float cnt = (float)cpg * (float)N;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int kk = (tid >> 5) + 8 * it, c = k0 + kk;
+      float v = 0.f;
+      if (live && c < a.K) {
+        const int g = c / cpg;
+        const float rstd = 1.0f / sqrtf(mom[2 * g + 1] / cnt + a.eps);
+        v = ((t.g[it] - mom[2 * g]) * rstd) * a.gamma[c] + a.beta[c];
+      }
+      s[(tid & 31) * GW_P + kk] = v;
+    }
+  } else if constexpr (PRO == GH_XF_PRO_LN) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int i = tid + it * GHR_BLOCK, r = i / 16, c = 4 * (i % 16);
+      const bool live = t0 + r < t_hi;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + c + j;
+        s[r * GW_P + c + j] = live && k < a.K ? ((t.w.v[it][j] - ln[it][0]) * ln[it][1]) * a.gamma[k] + a.beta[k] : 0.f;
+      }
+    }
+  } else {
+    gx_wput<PRO == GH_XF_PRO_CF>(t, s, tid);
+  }
+}
+
+template <int PRO, bool DYCF>
+__global__ __launch_bounds__(GHR_BLOCK) void gx_wgrad_kernel(GhXfWgrad a, int chunk, int nchunks, int ntj, int ntk, float* __restrict__ part_w,
+                                                              float* __restrict__ part_b, int vec_x, int vec_dy) {
+  __shared__ float s_dy[GW_TS * GW_P];
+  __shared__ float s_x[GW_TS * GW_P];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, half = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int tk = blockIdx.x % ntk, rest = blockIdx.x / ntk, tj = rest % ntj, ch = rest / ntj;
+  const int j0 = tj * 64, k0 = tk * 64;
+  const int t_lo = ch * chunk, t_hi = a.T - t_lo < chunk ? a.T : t_lo + chunk;
+  const bool want_w = a.dw != nullptr, want_b = a.db != nullptr && tk == 0;   // workgroup-uniform
+  constexpr bool XCF = gx_cf<PRO>;
+
+  ghr_acc acc = gx_splat(0.f);
+  float bsum = 0.f;
+  float ln[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+  GxWSlab xs, ds;
+  auto fetch = [&](int t0) {
+    gx_wfetch<DYCF>(ds, a.dy, a.dy_stride, a.dy_stride_b, a.rows_per_batch, t0, t_hi, j0, a.N_out, vec_dy, tid);
+    if (want_w) {
+      gx_wfetch<XCF>(xs, a.x, a.x_stride, a.x_stride_b, a.rows_per_batch, t0, t_hi, k0, a.K, vec_x, tid);
+      if constexpr (PRO == GH_XF_PRO_LN) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+          const int r = t0 + (tid + it * GHR_BLOCK) / 16;
+          if (r < t_hi) {
+            ln[it][0] = a.moments[2 * (long long)r];
+            ln[it][1] = a.moments[2 * (long long)r + 1];
+          }
+        }
+      }
+    }
+  };
+  fetch(t_lo);
+  for (int t0 = t_lo; t0 < t_hi; t0 += GW_TS) {
+    __syncthreads();                                           // the previous slab has been read by every wave
+    gx_wput<DYCF>(ds, s_dy, tid);
+    if (want_w) gx_wput_x<PRO>(xs, s_x, a, t0, t_hi, k0, ln, tid);
+    __syncthreads();
+    if (t0 + GW_TS < t_hi) fetch(t0 + GW_TS);                  // the next slab's loads fly under this slab's products
+    if (want_w) {
+      const float* ap = s_dy + half * GW_P + 32 * wr + col;
+      const float* bp = s_x + half * GW_P + 32 * wc + col;
+#pragma unroll
+      for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s * GW_P], bp[2 * s * GW_P], acc, 0, 0, 0);
+    }
+    if (want_b && wave == 0) {                                 // lane = column of the tile: one ascending chain over the rows
+      const int rl = t_hi - t0 < GW_TS ? t_hi - t0 : GW_TS;
+      for (int r = 0; r < rl; ++r) bsum += s_dy[r * GW_P + lane];
+    }
+  }
+
+  if (want_w) {
+    float* dst = nchunks > 1 ? part_w + (long long)ch * a.N_out * a.K : a.dw;
+    const int k = k0 + 32 * wc + col;
+    if (k < a.K) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = j0 + 32 * wr + ghr_acc_row(r, half);
+        if (j < a.N_out) dst[(long long)j * a.K + k] = acc[r];
+      }
+    }
+  }
+  if (want_b && wave == 0 && j0 + lane < a.N_out) (nchunks > 1 ? part_b + (long long)ch * a.N_out : a.db)[j0 + lane] = bsum;
+}
+
+// element e of dw (nw of them), then of db (nb): the chunks' partials in ascending order
+__global__ __launch_bounds__(GHR_BLOCK) void gx_wgrad_join_kernel(const float* __restrict__ part_w, long long nw, float* __restrict__ dw,
+                                                                   const float* __restrict__ part_b, int nb, float* __restrict__ db, int nchunks) {
+  const long long e = (long long)blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (e < nw) {
+    float s = part_w[e];
+    for (int c = 1; c < nchunks; ++c) s += part_w[c * nw + e];
+    dw[e] = s;
+  } else if (e - nw < nb) {
+    const long long j = e - nw;
+    float s = part_b[j];
+    for (int c = 1; c < nchunks; ++c) s += part_b[(long long)c * nb + j];
+    db[j] = s;
+  }
+}
+
+// ---- LayerNorm: dgamma and dbeta, two stages ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_ln_pgrad_part_kernel(const float* __restrict__ dn, long long dn_stride, const float* __restrict__ x,
+                                                                      long long x_stride, const float* __restrict__ mom, int T, int K, int nct,
+                                                                      float* __restrict__ part) {
+  __shared__ float s_red[2][4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ct = blockIdx.x % nct, rc = blockIdx.x / nct, k = ct * 64 + lane;
+  const long long r0 = (long long)rc * GH_XF_LNP_ROWS, r1 = r0 + GH_XF_LNP_ROWS < T ? r0 + GH_XF_LNP_ROWS : T;
+  float sg = 0.f, sb = 0.f;
+  if (k < K) {
+    for (long long r = r0 + wave; r < r1; r += 4) {
+      const float d = dn[r * dn_stride + k], xh = (x[r * x_stride + k] - mom[2 * r]) * mom[2 * r + 1];
+      sg = fmaf(d, xh, sg);
+      sb += d;
+    }
+  }
+  s_red[0][wave][lane] = sg;
+  s_red[1][wave][lane] = sb;
+  __syncthreads();
+  if (wave == 0 && k < K) {
+    part[(2 * (long long)rc) * K + k] = (s_red[0][0][lane] + s_red[0][1][lane]) + (s_red[0][2][lane] + s_red[0][3][lane]);
+    part[(2 * (long long)rc + 1) * K + k] = (s_red[1][0][lane] + s_red[1][1][lane]) + (s_red[1][2][lane] + s_red[1][3][lane]);
+  }
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_ln_pgrad_join_kernel(const float* __restrict__ part, int nrc, int K, float* __restrict__ dgamma,
+                                                                      float* __restrict__ dbeta) {
+  const int k = blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (k >= K) return;
+  float sg = part[k], sb = part[K + k];
+  for (int c = 1; c < nrc; ++c) {
+    sg += part[(2 * (long long)c) * K + k];
+    sb += part[(2 * (long long)c + 1) * K + k];
+  }
+  if (dgamma) dgamma[k] = sg;
+  if (dbeta) dbeta[k] = sb;
+}
+
+// ---- GroupNorm: dgamma and dbeta per channel, two stages ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(GHR_BLOCK) void gx_gn_pgrad_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                      const float* __restrict__ mom, int B, int C, int N, int G, int cpg, int nchunks,
+                                                                      float eps, float* __restrict__ part) {
+  __shared__ float s_red[4];
+  const int chunk = blockIdx.x % nchunks, bc = blockIdx.x / nchunks, b = bc / C, c = bc - b * C;
+  const int n = chunk * GH_XF_GN_CHUNK + threadIdx.x;
+  const long long bg = (long long)b * G + c / cpg, i = (long long)bc * N + n;
+  const float mean = mom[2 * bg], rstd = 1.0f / sqrtf(mom[2 * bg + 1] / ((float)cpg * (float)N) + eps);
+  float sg = 0.f, sb = 0.f;
+  if (n < N) {
+    sb = dy[i];
+    sg = sb * ((x[i] - mean) * rstd);
+  }
+  const float t1 = gx_block_sum(sg, s_red), t2 = gx_block_sum(sb, s_red);
+  if (threadIdx.x == 0) {
+    const long long o = 2 * (((long long)c * B + b) * nchunks + chunk);
+    part[o] = t1;
+    part[o + 1] = t2;
+  }
+}
+
+__global__ __launch_bounds__(GHR_BLOCK) void gx_gn_pgrad_join_kernel(const float* __restrict__ part, int C, int per, float* __restrict__ dgamma,
+                                                                      float* __restrict__ dbeta) {
+  const int c = blockIdx.x * GHR_BLOCK + threadIdx.x;
+  if (c >= C) return;
+  const float* p = part + 2 * (long long)c * per;
+  float sg = p[0], sb = p[1];
+  for (int i = 1; i < per; ++i) {
+    sg += p[2 * i];
+    sb += p[2 * i + 1];
+  }
+  if (dgamma) dgamma[c] = sg;
+  if (dbeta) dbeta[c] = sb;
+}
+
+// ---- host: the single launches of the parameters' gradients -------------------------------------------------------------------------------
+static int gx_wgrad_sizes_ok(long long T, int K, int N_out) {
+  return T >= 1 && T <= GH_XF_MAX_T && K >= 32 && K % 32 == 0 && K <= GH_XF_MAX_K && N_out >= 1 && N_out <= GH_XF_MAX_N_OUT;
+}
+
+extern "C" int gh_xf_linear_wgrad_chunk(int T, int K, int N_out) {
+  if (!gx_wgrad_sizes_ok(T, K, N_out)) return 0;
+  const long long tiles = (long long)((N_out + 63) / 64) * ((K + 63) / 64);
+  long long c = GH_XF_WGRAD_CHUNK;
+  while (c < T && tiles * ((T + c - 1) / c) > GH_XF_WGRAD_MAX_BLOCKS) c *= 2;
+  return (int)c;
+}
+
+extern "C" size_t gh_xf_linear_wgrad_workspace_bytes(int T, int K, int N_out) {
+  const int chunk = gh_xf_linear_wgrad_chunk(T, K, N_out);
+  if (chunk == 0) return 0;
+  const size_t nchunks = ((size_t)T + chunk - 1) / chunk;
+  if (nchunks <= 1) return 0;
+  return ghr_align(nchunks * N_out * K * sizeof(float)) + ghr_align(nchunks * N_out * sizeof(float));
+}
+
+template <int PRO>
+static void gx_launch_wgrad(const GhXfWgrad& a, int chunk, int nchunks, int ntj, int ntk, float* pw, float* pb, int vec_x, int vec_dy, int grid,
+                            hipStream_t s) {
+  const dim3 g((unsigned)grid), blk(GHR_BLOCK);
+  if (a.dy_cf) hipLaunchKernelGGL((gx_wgrad_kernel<PRO, true>), g, blk, 0, s, a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy);
+  else hipLaunchKernelGGL((gx_wgrad_kernel<PRO, false>), g, blk, 0, s, a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy);
+}
+
+extern "C" int gh_xf_linear_wgrad(const GhXfWgrad* a, void* workspace, size_t ws_bytes, void* hip_stream) {
+  if (!a || a->T < 0 || a->K < 1 || a->N_out < 1 || a->prologue < GH_XF_PRO_NONE || a->prologue > GH_XF_PRO_CF || (a->dy_cf != 0 && a->dy_cf != 1))
+    return GH_ERR_INVALID_ARG;
+  if (a->K % 32 != 0 || a->K > GH_XF_MAX_K || a->T > GH_XF_MAX_T || a->N_out > GH_XF_MAX_N_OUT) return GH_ERR_UNSUPPORTED;
+  const bool xcf = a->prologue == GH_XF_PRO_GN || a->prologue == GH_XF_PRO_CF;
+  const bool normed = a->prologue == GH_XF_PRO_LN || a->prologue == GH_XF_PRO_GN;
+  if ((xcf || a->dy_cf) && a->T > 0 && (a->rows_per_batch < 1 || a->T % a->rows_per_batch != 0)) return GH_ERR_INVALID_ARG;
+  if (a->prologue == GH_XF_PRO_GN && (a->groups < 1 || a->K % a->groups != 0 || !(a->eps >= 0.f && isfinite(a->eps)))) return GH_ERR_INVALID_ARG;
+  if (a->T == 0 || (!a->dw && !a->db)) return GH_OK;
+  if (!a->dy || !ghr_al4(a->dy) || !ghr_al4(a->dw) || !ghr_al4(a->db)) return GH_ERR_INVALID_ARG;
+  if (!a->dy_cf && a->dy_stride < a->N_out) return GH_ERR_INVALID_ARG;
+  if (a->dw) {
+    if (!a->x || !ghr_al4(a->x) || (!xcf && a->x_stride < a->K)) return GH_ERR_INVALID_ARG;
+    if (normed && (!a->gamma || !a->beta || !a->moments || !ghr_al4(a->gamma) || !ghr_al4(a->beta) || !ghr_al4(a->moments))) return GH_ERR_INVALID_ARG;
+  }
+  const int chunk = gh_xf_linear_wgrad_chunk(a->T, a->K, a->N_out), nchunks = (a->T + chunk - 1) / chunk;
+  const int ntj = (a->N_out + 63) / 64, ntk = a->dw ? (a->K + 63) / 64 : 1;
+  int grid;
+  if (gx_tiles((long long)nchunks * ntj, ntk, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;
+  float *pw = nullptr, *pb = nullptr;
+  const long long nw = (long long)a->N_out * a->K;
+  if (nchunks > 1) {
+    if (!workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+    if (ws_bytes < gh_xf_linear_wgrad_workspace_bytes(a->T, a->K, a->N_out)) return GH_ERR_WORKSPACE_SMALL;
+    pw = (float*)workspace;
+    pb = (float*)((char*)workspace + ghr_align((size_t)nchunks * nw * sizeof(float)));
+  }
+  const int vec_x = !xcf && a->x && ghr_al16(a->x) && a->x_stride % 4 == 0, vec_dy = !a->dy_cf && ghr_al16(a->dy) && a->dy_stride % 4 == 0;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  switch (a->prologue) {
+    case GH_XF_PRO_NONE: gx_launch_wgrad<GH_XF_PRO_NONE>(*a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy, grid, s); break;
+    case GH_XF_PRO_LN: gx_launch_wgrad<GH_XF_PRO_LN>(*a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy, grid, s); break;
+    case GH_XF_PRO_CF: gx_launch_wgrad<GH_XF_PRO_CF>(*a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy, grid, s); break;
+    default: gx_launch_wgrad<GH_XF_PRO_GN>(*a, chunk, nchunks, ntj, ntk, pw, pb, vec_x, vec_dy, grid, s); break;
+  }
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  if (nchunks > 1) {
+    const long long n_w = a->dw ? nw : 0;
+    const int n_b = a->db ? a->N_out : 0;
+    hipLaunchKernelGGL(gx_wgrad_join_kernel, dim3((unsigned)((n_w + n_b + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, (const float*)pw, n_w,
+                       a->dw, (const float*)pb, n_b, a->db, nchunks);
+    if (!gx_launched()) return GH_ERR_LAUNCH;
+  }
+  return GH_OK;
+}
+
+extern "C" size_t gh_xf_layernorm_param_grads_workspace_bytes(int T, int K) {
+  if (T <= 0 || T > GH_XF_MAX_T || K < 1 || K > GH_XF_MAX_K) return 0;
+  return ghr_align((size_t)((T + GH_XF_LNP_ROWS - 1) / GH_XF_LNP_ROWS) * 2 * K * sizeof(float));
+}
+
+extern "C" int gh_xf_layernorm_param_grads(const float* dn, int64_t dn_stride, const float* x, int64_t x_stride, const float* moments, int T, int K,
+                                           float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* hip_stream) {
+  if (T < 0 || K < 1) return GH_ERR_INVALID_ARG;
+  if (T > GH_XF_MAX_T || K > GH_XF_MAX_K) return GH_ERR_UNSUPPORTED;
+  if (T == 0 || (!dgamma && !dbeta)) return GH_OK;
+  const int nrc = (T + GH_XF_LNP_ROWS - 1) / GH_XF_LNP_ROWS, nct = (K + 63) / 64;
+  int grid;
+  if (gx_tiles(nrc, nct, &grid) != GH_OK) return GH_ERR_UNSUPPORTED;
+  const float* in[] = {dn, x, moments};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!ghr_al4(dgamma) || !ghr_al4(dbeta) || dn_stride < K || x_stride < K || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (ws_bytes < gh_xf_layernorm_param_grads_workspace_bytes(T, K)) return GH_ERR_WORKSPACE_SMALL;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_ln_pgrad_part_kernel, dim3((unsigned)grid), dim3(GHR_BLOCK), 0, s, dn, (long long)dn_stride, x, (long long)x_stride, moments, T,
+                     K, nct, (float*)workspace);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  hipLaunchKernelGGL(gx_ln_pgrad_join_kernel, dim3((unsigned)((K + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, (const float*)workspace, nrc, K,
+                     dgamma, dbeta);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
+extern "C" size_t gh_xf_group_norm_param_grads_workspace_bytes(int B, int C, int N, int G) {
+  bool empty;
+  if (gx_check_gn_bwd(B, C, N, G, &empty) != GH_OK || empty) return 0;
+  return ghr_align((size_t)B * C * ((N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK) * 2 * sizeof(float));
+}
+
+extern "C" int gh_xf_group_norm_param_grads(const float* dy, const float* x, const float* moments, int B, int C, int N, int G, float eps,
+                                            float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_gn_bwd(B, C, N, G, &empty);
+  if (rc != GH_OK) return rc;
+  if (!(eps >= 0.f && isfinite(eps))) return GH_ERR_INVALID_ARG;
+  if (empty || (!dgamma && !dbeta)) return GH_OK;
+  const float* in[] = {dy, x, moments};
+  for (const float* p : in) {
+    if (!p || !ghr_al4(p)) return GH_ERR_INVALID_ARG;
+  }
+  if (!ghr_al4(dgamma) || !ghr_al4(dbeta) || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
+  if (ws_bytes < gh_xf_group_norm_param_grads_workspace_bytes(B, C, N, G)) return GH_ERR_WORKSPACE_SMALL;
+  const int nchunks = (N + GH_XF_GN_CHUNK - 1) / GH_XF_GN_CHUNK;
+  if ((long long)B * nchunks > INT_MAX) return GH_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hip_stream;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gx_gn_pgrad_part_kernel, dim3((unsigned)(B * C * nchunks)), dim3(GHR_BLOCK), 0, s, dy, x, moments, B, C, N, G, C / G, nchunks, eps,
+                     (float*)workspace);
+  if (!gx_launched()) return GH_ERR_LAUNCH;
+  hipLaunchKernelGGL(gx_gn_pgrad_join_kernel, dim3((unsigned)((C + GHR_BLOCK - 1) / GHR_BLOCK)), dim3(GHR_BLOCK), 0, s, (const float*)workspace, C,
+                     B * nchunks, dgamma, dbeta);
+  return gx_launched() ? GH_OK : GH_ERR_LAUNCH;
+}
+
 // ---- host: the whole backward ------------------------------------------------------------------------------------------------------------
 // the workspace: the stream's cotangent g (T, M), dn (T, M), wide (T, 8M) — [da | dg], or datt (T, M) followed by dqkv (T, 3M) —, the
 // attention's delta, dy (B, C, N) of the GroupNorm, and the GroupNorm's partial sums
@@ -1300,13 +1669,38 @@ extern "C" size_t gh_xf_backward_workspace_bytes(const GhXfDims* dims) {
   return gx_back_plan(dims).total;
 }
 
-extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape_,
-                              const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream) {
-  bool empty;
-  int rc = gx_check_grad_dims(d, &empty);
-  if (rc != GH_OK) return rc;
-  if (empty) return GH_OK;
-  if (!stem || (d->layers > 0 && !layers) || !x || !dout || !dx || dx == x || dx == dout || !ghr_al4(x) || !ghr_al4(dout) || !ghr_al4(dx))
+// what gh_xf_backward_params adds to the chain: the forward's weights (the norms' shifts, and what forms a * gelu(g) and the final stream
+// again), where the gradients go, and its own parts of the workspace
+struct GxParamJob {
+  const GhXfStem* fs;
+  const GhXfLayer* fl;
+  const GhXfStemG* gs;
+  const GhXfLayerG* gl;
+  size_t ln, wg, np, total;                                    // the recomputed GEGLU's row moments; the product's partials; the norms' partials
+};
+
+static size_t gx_max(size_t a, size_t b) { return a > b ? a : b; }
+
+static void gx_param_plan(const GhXfDims* d, GxParamJob* j) {
+  const int T = d->B * d->N, M = d->heads * d->D, C = d->C;
+  size_t at = gx_back_plan(d).total;
+  j->ln = at; at += gh_xf_linear_workspace_bytes(T, GH_XF_PRO_LN);
+  size_t wg = gh_xf_linear_wgrad_workspace_bytes(T, M, C);
+  wg = gx_max(wg, gh_xf_linear_wgrad_workspace_bytes(T, C, M));
+  wg = gx_max(wg, gh_xf_linear_wgrad_workspace_bytes(T, 4 * M, M));
+  wg = gx_max(wg, gh_xf_linear_wgrad_workspace_bytes(T, M, 8 * M));
+  wg = gx_max(wg, gh_xf_linear_wgrad_workspace_bytes(T, M, M));
+  wg = gx_max(wg, gh_xf_linear_wgrad_workspace_bytes(T, M, 3 * M));
+  j->wg = at; at += wg;
+  j->np = at; at += gx_max(gh_xf_layernorm_param_grads_workspace_bytes(T, M), gh_xf_group_norm_param_grads_workspace_bytes(d->B, C, d->N, d->G));
+  j->total = at;
+}
+
+// pj == nullptr: the backward to x alone. Otherwise the same launches in the same order with the parameters' beside them.
+static int gx_backward(const GhXfDims* d, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape_, const float* dout,
+                       float* dx, void* workspace, size_t ws_bytes, void* hip_stream, const GxParamJob* pj) {
+  int rc;
+  if (!stem || (d->layers > 0 && !layers) || !x || !dout || (!dx && !pj) || dx == x || dx == dout || !ghr_al4(x) || !ghr_al4(dout) || !ghr_al4(dx))
     return GH_ERR_INVALID_ARG;
   const float* sp[] = {stem->gn_w, stem->in_t, stem->out_t};
   for (const float* p : sp) {
@@ -1322,7 +1716,7 @@ extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const Gh
   }
   if (!tape_ || !ghr_al16(tape_) || !workspace || !ghr_al16(workspace)) return GH_ERR_INVALID_ARG;
   const GxBackPlan p = gx_back_plan(d);
-  if (ws_bytes < p.total) return GH_ERR_WORKSPACE_SMALL;
+  if (ws_bytes < (pj ? pj->total : p.total)) return GH_ERR_WORKSPACE_SMALL;
   const GxTape tp = gx_tape(d);
   char* tape = (char*)tape_;                                   // read only
   char* ws = (char*)workspace;
@@ -1332,6 +1726,45 @@ extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const Gh
   float* dy = (float*)(ws + p.dy);
   const int T = d->B * d->N, M = d->heads * d->D, C = d->C, N = d->N;
 
+  // the lowest layer the chain has to reach, and whether it goes on through proj_in
+  bool below = true;
+  int lowest = 0;
+  if (pj) {
+    if (!pj->fs || !pj->gs || (d->layers > 0 && (!pj->fl || !pj->gl))) return GH_ERR_INVALID_ARG;
+    const float* fsp[] = {pj->fs->gn_w, pj->fs->gn_b, pj->fs->in_w, pj->fs->in_b, pj->fs->out_w, pj->fs->out_b};
+    for (const float* q : fsp) {
+      if (!q || !ghr_al4(q)) return GH_ERR_INVALID_ARG;
+    }
+    const float* gsp[] = {pj->gs->gn_w, pj->gs->gn_b, pj->gs->in_w, pj->gs->in_b, pj->gs->out_w, pj->gs->out_b};
+    for (const float* q : gsp) {
+      if (!ghr_al4(q)) return GH_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < d->layers; ++i) {
+      const GhXfLayer& F = pj->fl[i];
+      const float* need[] = {F.ln1_w, F.ln1_b, F.ln3_w, F.ln3_b, F.ff1_w, F.ff1_b, F.ff2_w, F.ff2_b};
+      for (const float* q : need) {
+        if (!q || !ghr_al4(q)) return GH_ERR_INVALID_ARG;
+      }
+      if (layers[i].qkv2_t && (!F.ln2_w || !F.ln2_b || !ghr_al4(F.ln2_w) || !ghr_al4(F.ln2_b))) return GH_ERR_INVALID_ARG;
+      const GhXfLayerG& Q = pj->gl[i];
+      const float* gq[] = {Q.ln1_w, Q.ln1_b, Q.qkv1, Q.o1_w, Q.o1_b, Q.ln2_w, Q.ln2_b, Q.qkv2, Q.o2_w, Q.o2_b, Q.ln3_w, Q.ln3_b, Q.ff1_w, Q.ff1_b, Q.ff2_w, Q.ff2_b};
+      for (const float* q : gq) {
+        if (!ghr_al4(q)) return GH_ERR_INVALID_ARG;
+      }
+    }
+    below = dx || pj->gs->gn_w || pj->gs->gn_b || pj->gs->in_w || pj->gs->in_b;
+    if (!below) {
+      lowest = d->layers;
+      for (int i = d->layers - 1; i >= 0; --i) {
+        const GhXfLayerG& Q = pj->gl[i];
+        const bool has2 = layers[i].qkv2_t != nullptr;
+        if (Q.ln1_w || Q.ln1_b || Q.qkv1 || Q.o1_w || Q.o1_b || Q.ln3_w || Q.ln3_b || Q.ff1_w || Q.ff1_b || Q.ff2_w || Q.ff2_b ||
+            (has2 && (Q.ln2_w || Q.ln2_b || Q.qkv2 || Q.o2_w || Q.o2_b)))
+          lowest = i;
+      }
+    }
+  }
+
   // y (T, n_out) = src (T, K) . wt^T, each element one ascending chain from zero
   auto data = [&](const float* src, int K, const float* wt, int n_out, float* y) {
     GhXfLinear l = {};
@@ -1339,6 +1772,57 @@ extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const Gh
     l.y_stride = n_out;
     return gh_xf_linear(&l, nullptr, 0, hip_stream);
   };
+  // dw (n_out, K) = dysrc^T . P(xsrc) and db = the column sums of dysrc, both over rows (T, .)
+  auto wgrad = [&](int pro, const float* xsrc, int K, const float* mom, const float* gamma, const float* beta, const float* dysrc, int n_out,
+                   float* dw, float* db) {
+    if (!dw && !db) return (int)GH_OK;
+    GhXfWgrad w = {};
+    w.T = T; w.K = K; w.N_out = n_out; w.prologue = pro; w.x = xsrc; w.x_stride = K; w.dy = dysrc; w.dy_stride = n_out; w.gamma = gamma;
+    w.beta = beta; w.moments = mom; w.dw = dw; w.db = db;
+    return gh_xf_linear_wgrad(&w, ws + pj->wg, pj->np - pj->wg, hip_stream);
+  };
+  auto norm_grads = [&](const float* dnp, const float* xp, const float* mom, float* dgamma, float* dbeta) {
+    return gh_xf_layernorm_param_grads(dnp, M, xp, M, mom, T, M, dgamma, dbeta, ws + pj->np, pj->total - pj->np, hip_stream);
+  };
+  // ff (T, 4M) = a * gelu(g) of layer i, by the forward's own launches, into `wide`
+  auto reform_ff = [&](int i) {
+    const char* fs = gx_slot(tp, tape, i, 2);
+    const GhXfLayer& F = pj->fl[i];
+    GhXfLinear l = {};
+    l.T = T; l.K = M; l.N_out = 4 * M; l.prologue = GH_XF_PRO_LN; l.epilogue = GH_XF_EPI_GEGLU; l.eps = d->ln_eps; l.x = (const float*)fs; l.x_stride = M;
+    l.w = F.ff1_w; l.bias = F.ff1_b; l.gamma = F.ln3_w; l.beta = F.ln3_b; l.y = wide; l.y_stride = 4 * M;
+    return gh_xf_linear(&l, ws + pj->ln, pj->wg - pj->ln, hip_stream);
+  };
+
+  bool ff_formed = false;                                      // `wide` holds the last layer's a * gelu(g)
+  if (pj && (pj->gs->out_w || pj->gs->out_b)) {
+    float* fin = dn;                                           // the final stream, in the buffer dn takes later
+    if (pj->gs->out_w) {
+      if (d->layers > 0) {
+        const int i = d->layers - 1;
+        rc = reform_ff(i);
+        if (rc != GH_OK) return rc;
+        ff_formed = true;
+        GhXfLinear l = {};
+        l.T = T; l.K = 4 * M; l.N_out = M; l.prologue = GH_XF_PRO_NONE; l.epilogue = GH_XF_EPI_BIAS_RES; l.x = wide; l.x_stride = 4 * M;
+        l.w = pj->fl[i].ff2_w; l.bias = pj->fl[i].ff2_b; l.res = (const float*)gx_slot(tp, tape, i, 2); l.res_stride = M; l.y = fin; l.y_stride = M;
+        rc = gh_xf_linear(&l, nullptr, 0, hip_stream);
+      } else {
+        GhXfLinear l = {};
+        l.T = T; l.K = C; l.N_out = M; l.prologue = GH_XF_PRO_GN; l.epilogue = GH_XF_EPI_BIAS_RES; l.rows_per_batch = N; l.groups = d->G;
+        l.eps = d->gn_eps; l.x = x; l.x_stride = N; l.x_stride_b = (int64_t)C * N; l.w = pj->fs->in_w; l.bias = pj->fs->in_b; l.gamma = pj->fs->gn_w;
+        l.beta = pj->fs->gn_b; l.moments = (const float*)(tape + tp.gn); l.y = fin; l.y_stride = M;
+        rc = gh_xf_linear(&l, nullptr, 0, hip_stream);
+      }
+      if (rc != GH_OK) return rc;
+    }
+    GhXfWgrad w = {};                                          // dW_out = dout_rows^T . fin, dout read channel first in place
+    w.T = T; w.K = M; w.N_out = C; w.prologue = GH_XF_PRO_NONE; w.dy_cf = 1; w.rows_per_batch = N; w.x = fin; w.x_stride = M; w.dy = dout;
+    w.dy_stride = N; w.dy_stride_b = (int64_t)C * N; w.dw = pj->gs->out_w; w.db = pj->gs->out_b;
+    rc = gh_xf_linear_wgrad(&w, ws + pj->wg, pj->np - pj->wg, hip_stream);
+    if (rc != GH_OK) return rc;
+  }
+  if (pj && !below && lowest >= d->layers) return GH_OK;       // nothing below proj_out is wanted
 
   GhXfLinear a = {};                                           // g = dout_rows . W_out, dout read channel first in place
   a.T = T; a.K = C; a.N_out = M; a.prologue = GH_XF_PRO_CF; a.epilogue = GH_XF_EPI_PLAIN; a.rows_per_batch = N; a.x = dout; a.x_stride = N;
@@ -1346,39 +1830,119 @@ extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const Gh
   rc = gh_xf_linear(&a, nullptr, 0, hip_stream);
   if (rc != GH_OK) return rc;
 
-  for (int i = d->layers - 1; i >= 0; --i) {
+  for (int i = d->layers - 1; i >= lowest; --i) {
     const GhXfLayerT& L = layers[i];
     const char* fs = gx_slot(tp, tape, i, 2);
-    rc = gh_xf_geglu_backward(g, M, (const float*)fs, M, (const float*)(fs + tp.f_ln), L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, L.ff2_t, T, M, wide,
-                              8 * (int64_t)M, hip_stream);
+    const float* fmom = (const float*)(fs + tp.f_ln);
+    if (pj && (pj->gl[i].ff2_w || pj->gl[i].ff2_b)) {          // before [da | dg] takes `wide`
+      if (pj->gl[i].ff2_w && !ff_formed) {
+        rc = reform_ff(i);
+        if (rc != GH_OK) return rc;
+      }
+      rc = wgrad(GH_XF_PRO_NONE, wide, 4 * M, nullptr, nullptr, nullptr, g, M, pj->gl[i].ff2_w, pj->gl[i].ff2_b);
+      if (rc != GH_OK) return rc;
+    }
+    ff_formed = false;
+    rc = gh_xf_geglu_backward(g, M, (const float*)fs, M, fmom, L.ln3_w, L.ln3_b, L.ff1_w, L.ff1_b, L.ff2_t, T, M, wide, 8 * (int64_t)M, hip_stream);
     if (rc != GH_OK) return rc;
+    if (pj) {
+      rc = wgrad(GH_XF_PRO_LN, (const float*)fs, M, fmom, pj->fl[i].ln3_w, pj->fl[i].ln3_b, wide, 8 * M, pj->gl[i].ff1_w, pj->gl[i].ff1_b);
+      if (rc != GH_OK) return rc;
+    }
     rc = data(wide, 8 * M, L.ff1_t, M, dn);
     if (rc != GH_OK) return rc;
-    rc = gh_xf_layernorm_backward(dn, M, (const float*)fs, M, (const float*)(fs + tp.f_ln), L.ln3_w, T, M, g, M, hip_stream);
+    if (pj) {
+      rc = norm_grads(dn, (const float*)fs, fmom, pj->gl[i].ln3_w, pj->gl[i].ln3_b);
+      if (rc != GH_OK) return rc;
+    }
+    rc = gh_xf_layernorm_backward(dn, M, (const float*)fs, M, fmom, L.ln3_w, T, M, g, M, hip_stream);
     if (rc != GH_OK) return rc;
     for (int which = 1; which >= 0; --which) {
       const float* wqkv_t = which ? L.qkv2_t : L.qkv1_t;
       if (!wqkv_t) continue;
       const char* as = gx_slot(tp, tape, i, which);
+      const float* amom = (const float*)(as + tp.a_ln);
       float* datt = wide;
       float* dqkv = wide + (size_t)T * M;
+      if (pj) {
+        const GhXfLayerG& Q = pj->gl[i];
+        rc = wgrad(GH_XF_PRO_NONE, (const float*)(as + tp.a_att), M, nullptr, nullptr, nullptr, g, M, which ? Q.o2_w : Q.o1_w, which ? Q.o2_b : Q.o1_b);
+        if (rc != GH_OK) return rc;
+      }
       rc = data(g, M, which ? L.o2_t : L.o1_t, M, datt);
       if (rc != GH_OK) return rc;
       rc = gh_xf_attention_backward((const float*)(as + tp.a_qkv), 3 * M, (const float*)(as + tp.a_att), M, (const float*)(as + tp.a_lse), datt, M,
                                     d->B, N, d->heads, d->D, dqkv, 3 * M, ws + p.delta, p.dy - p.delta, hip_stream);
       if (rc != GH_OK) return rc;
+      if (pj) {
+        const GhXfLayer& F = pj->fl[i];
+        rc = wgrad(GH_XF_PRO_LN, (const float*)as, M, amom, which ? F.ln2_w : F.ln1_w, which ? F.ln2_b : F.ln1_b, dqkv, 3 * M,
+                   which ? pj->gl[i].qkv2 : pj->gl[i].qkv1, nullptr);
+        if (rc != GH_OK) return rc;
+      }
       rc = data(dqkv, 3 * M, wqkv_t, M, dn);
       if (rc != GH_OK) return rc;
-      rc = gh_xf_layernorm_backward(dn, M, (const float*)as, M, (const float*)(as + tp.a_ln), which ? L.ln2_w : L.ln1_w, T, M, g, M, hip_stream);
+      if (pj) {
+        rc = norm_grads(dn, (const float*)as, amom, which ? pj->gl[i].ln2_w : pj->gl[i].ln1_w, which ? pj->gl[i].ln2_b : pj->gl[i].ln1_b);
+        if (rc != GH_OK) return rc;
+      }
+      rc = gh_xf_layernorm_backward(dn, M, (const float*)as, M, amom, which ? L.ln2_w : L.ln1_w, T, M, g, M, hip_stream);
       if (rc != GH_OK) return rc;
     }
   }
+  if (!below) return GH_OK;
+
+  if (pj && (pj->gs->in_w || pj->gs->in_b)) {                  // dW_in = g^T . GN(x), x read channel first through the norm
+    GhXfWgrad w = {};
+    w.T = T; w.K = C; w.N_out = M; w.prologue = GH_XF_PRO_GN; w.rows_per_batch = N; w.groups = d->G; w.eps = d->gn_eps; w.x = x; w.x_stride = N;
+    w.x_stride_b = (int64_t)C * N; w.dy = g; w.dy_stride = M; w.gamma = pj->fs->gn_w; w.beta = pj->fs->gn_b; w.moments = (const float*)(tape + tp.gn);
+    w.dw = pj->gs->in_w; w.db = pj->gs->in_b;
+    rc = gh_xf_linear_wgrad(&w, ws + pj->wg, pj->np - pj->wg, hip_stream);
+    if (rc != GH_OK) return rc;
+  }
+  if (!dx && !pj->gs->gn_w && !pj->gs->gn_b) return GH_OK;
 
   GhXfLinear z = {};                                           // dy = g . W_in, written channel first; neither bias nor residual
   z.T = T; z.K = M; z.N_out = C; z.prologue = GH_XF_PRO_NONE; z.epilogue = GH_XF_EPI_BIAS_RES_CF; z.rows_per_batch = N; z.x = g; z.x_stride = M;
   z.w = stem->in_t; z.y = dy; z.y_stride = N; z.y_stride_b = (int64_t)C * N;
   rc = gx_linear(&z, nullptr, 0, hip_stream, false);
   if (rc != GH_OK) return rc;
+  if (pj) {
+    rc = gh_xf_group_norm_param_grads(dy, x, (const float*)(tape + tp.gn), d->B, C, N, d->G, d->gn_eps, pj->gs->gn_w, pj->gs->gn_b, ws + pj->np,
+                                      pj->total - pj->np, hip_stream);
+    if (rc != GH_OK) return rc;
+  }
+  if (!dx) return GH_OK;
   return gh_xf_group_norm_backward(dy, x, (const float*)(tape + tp.gn), stem->gn_w, dout, dx, d->B, C, N, d->G, d->gn_eps, ws + p.gnw,
                                    p.total - p.gnw, hip_stream);
+}
+
+extern "C" int gh_xf_backward(const GhXfDims* d, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape,
+                              const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_grad_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  return gx_backward(d, stem, layers, x, tape, dout, dx, workspace, ws_bytes, hip_stream, nullptr);
+}
+
+extern "C" size_t gh_xf_backward_params_workspace_bytes(const GhXfDims* dims) {
+  bool empty;
+  if (gx_check_grad_dims(dims, &empty) != GH_OK || empty) return 0;
+  GxParamJob j = {};
+  gx_param_plan(dims, &j);
+  return j.total;
+}
+
+extern "C" int gh_xf_backward_params(const GhXfDims* d, const GhXfStemT* stem, const GhXfLayerT* layers, const GhXfStem* fstem,
+                                     const GhXfLayer* flayers, const GhXfStemG* gstem, const GhXfLayerG* glayers, const float* x, const void* tape,
+                                     const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream) {
+  bool empty;
+  const int rc = gx_check_grad_dims(d, &empty);
+  if (rc != GH_OK) return rc;
+  if (empty) return GH_OK;
+  GxParamJob j = {};
+  j.fs = fstem; j.fl = flayers; j.gs = gstem; j.gl = glayers;
+  gx_param_plan(d, &j);
+  return gx_backward(d, stem, layers, x, tape, dout, dx, workspace, ws_bytes, hip_stream, &j);
 }

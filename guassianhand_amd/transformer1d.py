@@ -21,6 +21,12 @@ gh_xf_backward: 5 + 13 launches per layer, float32, no atomics, bitwise reproduc
 (GH_XF_GRAD_MAX_M). A parameter that requires a gradient is the reason "a parameter wants a gradient" and the torch path; with nothing
 requiring a gradient the plain untaped kernels run. grad="none", the default, is the forward-only behaviour exactly.
 
+grad="params" adds training: where a parameter requires a gradient the call is a second torch.autograd.Function over x and the
+parameter tensors, whose forward is the same gh_xf_forward_tape and whose backward is gh_xf_backward_params: gh_xf_backward's chain (dx
+bitwise the same) with, beside each step, the backward-weight products, the bias sums and the norms' scale and shift sums of the
+parameters that want a gradient, and of those alone. The gradients of to_q, to_k and to_v are the row blocks of one stacked gradient.
+With only x requiring a gradient it is grad="input"'s function, with nothing requiring one the plain kernels; M <= 512 as there.
+
 `transformer1d_ref(params, x, acc=None)` is the plain-torch restatement with an explicit softmax, so that it runs in float64 (the
 yardstick of the GPU tests); it is written from transformers.py and the attribute layout of diffusers' Attention and is not pinned
 against a recorded run of the reference. `params_of(module)` reads the nested parameter dict off any module with that layout.
@@ -28,7 +34,8 @@ against a recorded run of the reference. `params_of(module)` reads the nested pa
 class for `fused_transformer1d_cls` of its own class; the concatenated [Wq; Wk; Wv] are cached per module and rebuilt when a
 parameter's version counter (or storage) changes, and so are the transposed copies the backward's data products read, built when a
 backward first needs them; `refresh(module)` drops them by hand. `linear`, `group_moments` and `attention` are the forward's single
-launches; `attention_lse`, `attention_backward`, `geglu_backward`, `layernorm_backward` and `group_norm_backward` the backward's."""
+launches; `attention_lse`, `attention_backward`, `geglu_backward`, `layernorm_backward` and `group_norm_backward` the backward's;
+`linear_wgrad`, `layernorm_param_grads` and `group_norm_param_grads` those of the parameters' gradients."""
 from __future__ import annotations
 
 import ctypes as C
@@ -44,7 +51,7 @@ from ._call import check_ops, cotangent, launch, lib, ptr, row_stride, rows, wor
 
 HEAD_DIMS = (32, 64)
 MAX_M, MAX_C, MAX_T, GRAD_MAX_M = _abi.GH_XF_MAX_M, _abi.GH_XF_MAX_C, _abi.GH_XF_MAX_T, _abi.GH_XF_GRAD_MAX_M
-GRADS = ("none", "input")
+GRADS = ("none", "input", "params")
 PROLOGUES = {"none": _abi.GH_XF_PRO_NONE, "ln": _abi.GH_XF_PRO_LN, "gn": _abi.GH_XF_PRO_GN, "cf": _abi.GH_XF_PRO_CF}
 EPILOGUES = {"plain": _abi.GH_XF_EPI_PLAIN, "bias_res": _abi.GH_XF_EPI_BIAS_RES, "geglu": _abi.GH_XF_EPI_GEGLU,
              "bias_res_cf": _abi.GH_XF_EPI_BIAS_RES_CF}
@@ -280,6 +287,77 @@ def group_norm_backward(dy, x, moments, gamma, dout, groups: int, eps: float = G
     return dx
 
 
+# ---- the single launches of the parameters' gradients ---------------------------------------------------------------------------------
+def linear_wgrad_chunk(T: int, K: int, n_out: int) -> int:
+    """Rows per chunk of `linear_wgrad`'s split of T: a function of the three sizes alone."""
+    return int(lib().gh_xf_linear_wgrad_chunk(int(T), int(K), int(n_out)))
+
+
+def linear_wgrad(dy, x, *, prologue="none", gamma=None, beta=None, eps=GN_EPS, moments=None, groups=0, want_w=True, want_b=True):
+    """One gh_xf_linear_wgrad call: (dW (N_out, K), db (N_out)) = (dY^T P(X), the column sums of dY) over the T rows; either is None
+    where not wanted. x: (T, K) rows read in place, or under prologue="gn" and "cf" the channel-first (B, K, N); dy: (T, N_out) rows
+    read in place, or a 3-D channel-first (B, N_out, N). moments: the (T, 2) {mean, rstd} rows under "ln", `group_moments`' under "gn"."""
+    a = _abi.GhXfWgrad()
+    rpb = 0
+    if prologue in ("gn", "cf"):
+        if x.shape[2] > 1 and x.stride(2) != 1:
+            x = x.contiguous()
+        B, K, N = x.shape
+        T, rpb = B * N, N
+        a.x_stride, a.x_stride_b = int(x.stride(1)), int(x.stride(0))
+    else:
+        x = rows(x)
+        T, K = x.shape
+        a.x_stride = row_stride(x)
+    if dy.dim() == 3:
+        if dy.shape[2] > 1 and dy.stride(2) != 1:
+            dy = dy.contiguous()
+        n_out, rpb = dy.shape[1], dy.shape[2]
+        a.dy_cf, a.dy_stride, a.dy_stride_b = 1, int(dy.stride(1)), int(dy.stride(0))
+    else:
+        dy = rows(dy)
+        n_out = dy.shape[1]
+        a.dy_stride = row_stride(dy)
+    dev = x.device
+    dw = torch.empty(n_out, K, dtype=torch.float32, device=dev) if want_w else None
+    db = torch.empty(n_out, dtype=torch.float32, device=dev) if want_b else None
+    if T == 0:
+        return (None if dw is None else dw.zero_()), (None if db is None else db.zero_())
+    keep = [None if t is None else t.contiguous() for t in (gamma, beta, moments)]
+    a.T, a.K, a.N_out, a.prologue, a.rows_per_batch, a.groups, a.eps = T, K, n_out, PROLOGUES[prologue], int(rpb), int(groups), float(eps)
+    a.x, a.dy = x.data_ptr(), dy.data_ptr()
+    a.gamma, a.beta, a.moments = (None if t is None else t.data_ptr() for t in keep)
+    a.dw, a.db = (None if t is None else t.data_ptr() for t in (dw, db))
+    nbytes = int(lib().gh_xf_linear_wgrad_workspace_bytes(T, K, n_out))
+    ws = workspace(nbytes, dev)
+    launch("gh_xf_linear_wgrad", dev, C.byref(a), ptr(ws), nbytes, detail=f" (T={T}, K={K}, N_out={n_out}, {prologue})")
+    return dw, db
+
+
+def layernorm_param_grads(dn, x, moments):
+    """(dgamma, dbeta) (K) of a LayerNorm whose output's cotangent is dn (T, K), at x (T, K) with row moments (T, 2) {mean, rstd}."""
+    dn, x = rows(dn), rows(x)
+    T, K = x.shape
+    dg, db = torch.zeros(K, dtype=torch.float32, device=x.device), torch.zeros(K, dtype=torch.float32, device=x.device)
+    nbytes = int(lib().gh_xf_layernorm_param_grads_workspace_bytes(T, K))
+    ws, mom = workspace(nbytes, x.device), moments.contiguous()
+    launch("gh_xf_layernorm_param_grads", x.device, ptr(dn), row_stride(dn), ptr(x), row_stride(x), ptr(mom), T, K, ptr(dg), ptr(db), ptr(ws),
+           nbytes, detail=f" (T={T}, K={K})")
+    return dg, db
+
+
+def group_norm_param_grads(dy, x, moments, groups: int, eps: float = GN_EPS):
+    """(dgamma, dbeta) (C) of the GroupNorm whose output's cotangent is dy (B, C, N), at x with `group_moments`' moments."""
+    dy, x = dy.contiguous(), x.contiguous()
+    B, Cc, N = x.shape
+    dg, db = torch.zeros(Cc, dtype=torch.float32, device=x.device), torch.zeros(Cc, dtype=torch.float32, device=x.device)
+    nbytes = int(lib().gh_xf_group_norm_param_grads_workspace_bytes(B, Cc, N, groups))
+    ws, mom = workspace(nbytes, x.device), moments.contiguous()
+    launch("gh_xf_group_norm_param_grads", x.device, ptr(dy), ptr(x), ptr(mom), B, Cc, N, groups, float(eps), ptr(dg), ptr(db), ptr(ws), nbytes,
+           detail=f" (B={B}, C={Cc}, N={N}, G={groups})")
+    return dg, db
+
+
 # ---- the whole stack ------------------------------------------------------------------------------------------------------------------
 class _Packed:
     """The parameters as gh_xf_forward reads them: contiguous float32 tensors (kept alive here), the concatenated [Wq; Wk; Wv], and
@@ -380,6 +458,75 @@ def _run_backward(packed: _Packed, x: torch.Tensor, tape: torch.Tensor, dout: to
     return dx
 
 
+def _grad_slots(params):
+    """Parallel to `_tensors(params)`: where each tensor's gradient lies among gh_xf_backward_params' buffers, as (layer index or None
+    for the stem, the GhXfStemG / GhXfLayerG field, the row block of a stacked [Wq; Wk; Wv] gradient or None)."""
+    out = [(None, n, None) for n in _abi.XF_STEM]
+    for i, b in enumerate(params["blocks"]):
+        for k, names in (("norm1", ("ln1_w", "ln1_b")), ("norm2", ("ln2_w", "ln2_b")), ("norm3", ("ln3_w", "ln3_b")), ("ff1", ("ff1_w", "ff1_b")),
+                         ("ff2", ("ff2_w", "ff2_b"))):
+            if b[k] is not None:
+                out += [(i, n, None) for n in names]
+        for k, n in (("attn1", "1"), ("attn2", "2")):
+            if b[k] is not None:
+                out += [(i, "qkv" + n, 0), (i, "qkv" + n, 1), (i, "qkv" + n, 2), (i, f"o{n}_w", None), (i, f"o{n}_b", None)]
+    return out
+
+
+def _run_backward_params(packed: _Packed, x, tape, dout, slots, shapes, needs, want_dx: bool):
+    """gh_xf_backward_params: (dx or None, the gradients parallel to `slots`, None where `needs` says so). Buffers exist only for what
+    is wanted; the three attention weights share one stacked buffer."""
+    dims = _dims(packed, x)
+    stem_t, layers_t = packed.transposed()
+    M, dev = packed.M, x.device
+    bufs = {}
+    for (layer, field, block), shape, need in zip(slots, shapes, needs):
+        if need and (layer, field) not in bufs:
+            bufs[(layer, field)] = torch.empty((3 * M, M) if block is not None else shape, dtype=torch.float32, device=dev)
+    gstem = _abi.GhXfStemG(*[bufs[(None, n)].data_ptr() if (None, n) in bufs else None for n in _abi.XF_STEM])
+    glayers = (_abi.GhXfLayerG * max(packed.n_layers, 1))()
+    for (layer, field), t in bufs.items():
+        if layer is not None:
+            setattr(glayers[layer], field, t.data_ptr())
+    dx = torch.empty_like(x) if want_dx else None
+    nbytes = int(lib().gh_xf_backward_params_workspace_bytes(C.byref(dims)))
+    ws = workspace(nbytes, dev)
+    launch("gh_xf_backward_params", dev, C.byref(dims), C.byref(stem_t), layers_t, C.byref(packed.stem), packed.layers, C.byref(gstem), glayers,
+           ptr(x), ptr(tape), ptr(dout), ptr(dx), ptr(ws), nbytes, detail=_detail(packed, x))
+    grads = []
+    for (layer, field, block), need in zip(slots, needs):
+        t = bufs[(layer, field)] if need else None
+        grads.append(t if t is None or block is None else t[block * M:(block + 1) * M])
+    return dx, grads
+
+
+class _ParamGrad(torch.autograd.Function):
+    """The stack with its backward to x and to every parameter that wants a gradient: gh_xf_forward_tape, then gh_xf_backward_params.
+    The inputs behind `packed` are the parameter tensors in `_tensors` order."""
+
+    @staticmethod
+    def forward(ctx, x, packed, slots, *tensors):
+        xc = x.detach().contiguous()
+        ctx.packed, ctx.slots, ctx.shapes = packed, slots, [tuple(t.shape) for t in tensors]
+        if xc.shape[0] == 0 or xc.shape[2] == 0:
+            ctx.save_for_backward(xc)
+            return torch.empty_like(xc)
+        out, tape = _run_tape(packed, xc)
+        ctx.save_for_backward(xc, tape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        needs = ctx.needs_input_grad
+        xc = ctx.saved_tensors[0]
+        if len(ctx.saved_tensors) == 1:
+            zeros = [torch.zeros(s, dtype=torch.float32, device=xc.device) if n else None for s, n in zip(ctx.shapes, needs[3:])]
+            return (torch.zeros_like(xc) if needs[0] else None, None, None, *zeros)
+        dx, grads = _run_backward_params(ctx.packed, xc, ctx.saved_tensors[1], cotangent(dout), ctx.slots, ctx.shapes, needs[3:], needs[0])
+        return (dx, None, None, *grads)
+
+
 class _InputGrad(torch.autograd.Function):
     """The stack with its backward to x: gh_xf_forward_tape, then gh_xf_backward. The weights are constants."""
 
@@ -403,16 +550,22 @@ class _InputGrad(torch.autograd.Function):
         return _run_backward(ctx.packed, xc, tape, cotangent(dout)), None
 
 
-def _go(packed: _Packed, x: torch.Tensor, grad: str) -> torch.Tensor:
-    """The kernels for a call kernel_reason let through: taped where grad="input" has a gradient to carry, else plain."""
-    if grad == "input" and torch.is_grad_enabled() and x.requires_grad:
-        return _InputGrad.apply(x, packed)
+def _go(packed: _Packed, x: torch.Tensor, grad: str, params=None) -> torch.Tensor:
+    """The kernels for a call kernel_reason let through: plain where nothing wants a gradient, taped with the backward to x where x
+    alone does, taped with the parameters' backward (grad="params") where a parameter does."""
+    if grad != "none" and torch.is_grad_enabled():
+        if grad == "params" and params is not None:
+            ts = _tensors(params)
+            if any(t.requires_grad for t in ts):
+                return _ParamGrad.apply(x, packed, _grad_slots(params), *ts)
+        if x.requires_grad:
+            return _InputGrad.apply(x, packed)
     return _run(packed, x)
 
 
 def _check_grad(grad: str) -> None:
     if grad not in GRADS:
-        raise ValueError(f"grad must be 'none' or 'input', got {grad!r}")
+        raise ValueError(f"grad must be one of {', '.join(repr(g) for g in GRADS)}, got {grad!r}")
 
 
 def _params_reason(params, x, grad: str = "none") -> Optional[str]:
@@ -430,7 +583,7 @@ def _params_reason(params, x, grad: str = "none") -> Optional[str]:
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in ts)):
         if grad == "none":
             return "a gradient is wanted"
-        if any(t.requires_grad for t in ts):
+        if grad != "params" and any(t.requires_grad for t in ts):
             return "a parameter wants a gradient"
         taped = True
     M, Cin = params["proj_in"][0].shape
@@ -522,7 +675,7 @@ def refresh(module) -> None:
 def kernel_reason(module_or_params, x, *, encoder_hidden_states=None, attention_mask=None, encoder_attention_mask=None,
                   grad: str = "none") -> Optional[str]:
     """None where transformer1d runs the kernels for this call, else the first condition that fails. grad="input": a gradient wanted
-    by x alone is no reason."""
+    by x alone is no reason. grad="params": nor is one wanted by a parameter."""
     _check_grad(grad)
     if encoder_hidden_states is not None or attention_mask is not None or encoder_attention_mask is not None:
         return "encoder_hidden_states or a mask"
@@ -534,14 +687,15 @@ def kernel_reason(module_or_params, x, *, encoder_hidden_states=None, attention_
 def transformer1d(module_or_params, x, *, ops: str = "fused", grad: str = "none", encoder_hidden_states=None, attention_mask=None,
                   encoder_attention_mask=None):
     """x (B, C, N) -> (B, C, N): the backbone's forward. ops="fused" runs the kernels where kernel_reason allows and the restatement
-    everywhere else; ops="torch" always the restatement. grad="input": the kernels also carry the gradient to x."""
+    everywhere else; ops="torch" always the restatement. grad="input": the kernels also carry the gradient to x; grad="params": and to
+    every parameter that requires one."""
     check_ops(ops)
     _check_grad(grad)
     is_params = isinstance(module_or_params, dict)
     extra = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
     if ops == "fused" and kernel_reason(module_or_params, x, grad=grad, **extra) is None:
         params = module_or_params if is_params else params_of(module_or_params)
-        return _go(_Packed(params) if is_params else _packed_of(module_or_params, params), x, grad)
+        return _go(_Packed(params) if is_params else _packed_of(module_or_params, params), x, grad, params)
     return transformer1d_ref(module_or_params if is_params else params_of(module_or_params), x, **extra)
 
 
@@ -611,6 +765,8 @@ class Transformer1D(nn.Module):
 
 # ---- the seam: a built module's forward ------------------------------------------------------------------------------------------------
 _fused_cls = {}
+_SEAM_DOC = {"none": "", "input": " and backward to the input",
+             "params": " and backward to the input and to every parameter that requires a gradient (gh_xf_backward_params)"}
 
 
 def _new_fused(base, grad="none"):
@@ -620,7 +776,8 @@ def _new_fused(base, grad="none"):
 
 def fused_transformer1d_cls(base, grad: str = "none"):
     """A subclass of the given Transformer1D class whose forward runs the kernels where kernel_reason allows and is the base class's
-    own forward, with the caller's arguments, everywhere else. grad="input": the kernels also carry the gradient to the input."""
+    own forward, with the caller's arguments, everywhere else. grad="input": the kernels also carry the gradient to the input;
+    grad="params": and to every parameter that requires one."""
     _check_grad(grad)
     if (base, grad) not in _fused_cls:
         def forward(self, hidden_states, encoder_hidden_states=None, timestep=None, modulation_cond=None, class_labels=None,
@@ -630,7 +787,8 @@ def fused_transformer1d_cls(base, grad: str = "none"):
             masks = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
             asks = masks if grad == "none" else dict(masks, grad=grad)
             if not cross_attention_kwargs and kernel_reason(self, hidden_states, **asks) is None:
-                return _go(_packed_of(self, params_of(self)), hidden_states, grad)
+                params = params_of(self)
+                return _go(_packed_of(self, params), hidden_states, grad, params)
             kw = dict(masks, timestep=timestep, modulation_cond=modulation_cond, class_labels=class_labels, cross_attention_kwargs=cross_attention_kwargs)
             return base.forward(self, hidden_states, **{k: v for k, v in kw.items() if v is not None})
 
@@ -638,7 +796,7 @@ def fused_transformer1d_cls(base, grad: str = "none"):
             # the class is made at run time and no module attribute names it: a pickle rebuilds it from its base
             return _new_fused, (base, grad), self.__dict__
 
-        doc = f"{base.__module__}.{base.__name__} with the MI355X fused forward" + (" and backward to the input" if grad == "input" else "")
+        doc = f"{base.__module__}.{base.__name__} with the MI355X fused forward" + _SEAM_DOC[grad]
         _fused_cls[(base, grad)] = type(base.__name__, (base,), {"forward": forward, "__reduce_ex__": reduce_ex, "__module__": __name__,
                                                                  "__doc__": doc, "_gh_base": base, "_gh_grad": grad})
     return _fused_cls[(base, grad)]

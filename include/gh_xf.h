@@ -3,7 +3,8 @@
  * (tgs/models/transformers.py:673-908, called at infer_one_shot.py:256-264) ask of a GroupNorm, about 85 library launches of
  * dense float32 GEMMs, LayerNorms, SDPA and a GEGLU per forward. The forward serves frozen inference; a second, opt-in path keeps
  * a tape and backpropagates to the input x alone, every weight frozen (the one-shot fit's identity code reaches the loss through
- * the texture backbone). Wherever a parameter wants a gradient the Python layer falls back to torch.
+ * the texture backbone). A third path, opt-in as well, reads the same tape and also returns the gradient of every parameter that
+ * wants one (gh_xf_backward_params): fine-tuning a few layers, or training the prior.
  *
  * The module's mathematics, written from transformers.py and the attribute layout of diffusers' Attention (not pinned against
  * a recorded run of the reference):
@@ -35,6 +36,8 @@
  *                        matrix is written and there is no lse output (gh_xf_attention_lse has one).
  *   gh_xf_forward        the whole stack, enqueued from C++ in one host call: 4 + 11 launches per layer (7 where attn2 is
  *                        absent).
+ *   gh_xf_backward_params  gh_xf_backward plus the gradients of the parameters that want one ("The parameters' gradients" below);
+ *                        gh_xf_linear_wgrad, gh_xf_layernorm_param_grads and gh_xf_group_norm_param_grads are its single launches.
  *
  * Supported sizes. D in {32, 64}; M = heads * D <= GH_XF_MAX_M; C a multiple of G and of 32, C <= GH_XF_MAX_C; K a multiple
  * of 32 and <= GH_XF_MAX_K and N_out <= GH_XF_MAX_N_OUT in gh_xf_linear; any N >= 1 and B >= 1 with B * N <= GH_XF_MAX_T and every launch's workgroup count
@@ -105,6 +108,34 @@
  *              ascending order; rstd = 1 / sqrtf(m2 / (cpg N) + eps) as the prologue forms it. Then one element-wise channel-first
  *              pass: dx = dout + rstd * ((w - s1 / (cpg N)) - xh * (s2 / (cpg N))); the + dout is the residual + x of the output.
  *
+ * The parameters' gradients. gh_xf_backward_params is gh_xf_backward — the same launches in the same order on the same buffers, dx
+ * bitwise the same — with the parameter-gradient launches enqueued beside each step. Two activations are not on the tape and are formed
+ * again with the forward's own launches: a * gelu(g) (T, 4M) by gh_xf_linear LN + GEGLU over the feed-forward slot's h, and for the last
+ * layer the final stream by one BIAS_RES launch on top of it (with no layer: the proj_in launch). A NULL gradient pointer is "not
+ * wanted": its launches are skipped and nothing is written; a gradient's bits do not depend on which others are asked for. Layers below
+ * the lowest one that wants anything are not visited when neither dx nor a stem gradient below them is wanted.
+ *   product    gh_xf_linear_wgrad: dW[j][k] = sum over t of dY[t][j] * P(X)[t][k], db[j] = sum over t of dY[t][j]. P is a forward
+ *              prologue re-applied from stored moments (LN: rows {mean, rstd}; GN: (B, G, 2) {mean, m2}, rstd = 1 / sqrtf(m2 / (cpg N) +
+ *              eps)) exactly as the forward's product forms it; dY is rows or channel first. A workgroup of 4 waves owns 64 (j) x 64
+ *              (k) outputs of one chunk of rows, a wave 32 x 32; dY and P(X) cross LDS in slabs of 32 rows; the products are
+ *              v_mfma_f32_32x32x2_f32. The rows are split into chunks of R = gh_xf_linear_wgrad_chunk(T, K, N_out): R =
+ *              GH_XF_WGRAD_CHUNK, doubled while R < T and (number of 64 x 64 output tiles) * ceil(T / R) > GH_XF_WGRAD_MAX_BLOCKS — a
+ *              function of T, K and N_out alone, the same whether dW, db or both are asked for. Within chunk c each dW element is one
+ *              ascending fmaf chain over t = c R .. min(T, (c + 1) R) - 1 from zero, each db element one ascending chain of
+ *              additions over the same t from zero (formed by the workgroups of the first k tile). Rows past T enter as zeros on both
+ *              sides and are never read. With one chunk the results go straight to dW and db; otherwise the partials land in the
+ *              workspace, (chunks, N_out, K) and (chunks, N_out), and a second launch joins them per element in ascending chunk order,
+ *              ((p0 + p1) + p2) + ...
+ *   LayerNorm  gh_xf_layernorm_param_grads: dgamma[k] = sum dn[t][k] * xh[t][k], dbeta[k] = sum dn[t][k], xh = (x - mean) * rstd from
+ *              the taped row moments. Stage one: a workgroup per (chunk of GH_XF_LNP_ROWS rows, 64 columns), lane = column; wave w
+ *              takes the chunk's rows w, w + 4, ... in ascending order, dgamma by fmaf(dn, xh, .) from zero, dbeta by addition from
+ *              zero; the four waves are added as (s0 + s1) + (s2 + s3). Stage two: one thread per column adds the chunks in ascending
+ *              order from chunk 0's partial.
+ *   GroupNorm  gh_xf_group_norm_param_grads: the same two sums per channel over (b, n), xh = (x - mean) * rstd with rstd = 1 / sqrtf(m2 /
+ *              (cpg N) + eps) as the prologue forms it. Stage one: a workgroup per (batch, channel, chunk of GH_XF_GN_CHUNK positions),
+ *              thread = position with the one term dy * xh (and dy), the wave butterfly, (s0 + s1) + (s2 + s3). Stage two: one thread
+ *              per channel adds the partials in ascending (batch, chunk) order from the first.
+ *
  * Conventions are those of gh_pool.h: caller-allocated buffers, all work enqueued on `hip_stream`, no host synchronisation, no
  * allocation, nothing thrown, HIP-graph capturable; GhStatus return codes, returned before any launch for bad arguments or a
  * short workspace. Strides are in float elements. All pointers 4-byte aligned, a workspace 16-byte aligned. An input whose
@@ -133,6 +164,10 @@ extern "C" {
 #define GH_XF_ATTN_BWD_ROWS 128 /* queries (dq) or keys (dk, dv) per workgroup of the attention's backward: 32 per wave */
 #define GH_XF_ATTN_BWD_STAGE 64 /* rows of the swept operand per LDS stage of the attention's backward */
 #define GH_XF_GRAD_MAX_M 512    /* the backward to x: 8 M <= GH_XF_MAX_K */
+#define GH_XF_WGRAD_ROWS 32     /* rows of dY and X per LDS slab of the backward-weight product */
+#define GH_XF_WGRAD_CHUNK 256   /* the smallest chunk of rows the backward-weight product splits T into */
+#define GH_XF_WGRAD_MAX_BLOCKS 1024 /* the chunk doubles while tiles * chunks exceeds this */
+#define GH_XF_LNP_ROWS 64       /* rows per stage-one workgroup of the LayerNorm's parameter gradients */
 
 #define GH_XF_PRO_NONE 0
 #define GH_XF_PRO_LN 1
@@ -265,6 +300,69 @@ int gh_xf_forward_tape(const GhXfDims* dims, const GhXfStem* stem, const GhXfLay
 size_t gh_xf_backward_workspace_bytes(const GhXfDims* dims);
 int gh_xf_backward(const GhXfDims* dims, const GhXfStemT* stem, const GhXfLayerT* layers, const float* x, const void* tape,
                    const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* ---- the parameters' gradients ---- */
+
+typedef struct GhXfWgrad {
+  int32_t T, K, N_out;      /* rows summed over, width of X (a multiple of 32), width of dY */
+  int32_t prologue;         /* of X: GH_XF_PRO_* */
+  int32_t dy_cf;            /* 0: dY is (T, N_out) rows. 1: channel first, element (t, j) at dy[b * dy_stride_b + j * dy_stride + n] */
+  int32_t rows_per_batch;   /* N: PRO_GN, PRO_CF and dy_cf (T a multiple of it); ignored otherwise */
+  int32_t groups;           /* PRO_GN: K a multiple of it */
+  float eps;                /* PRO_GN */
+  const float* x;           /* as GhXfLinear's x; may be NULL where dw is */
+  int64_t x_stride, x_stride_b;
+  const float* dy;
+  int64_t dy_stride, dy_stride_b;
+  const float* gamma;       /* K: PRO_LN, PRO_GN */
+  const float* beta;
+  const float* moments;     /* PRO_LN: (T, 2) {mean, rstd}. PRO_GN: (T / rows_per_batch, groups, 2) {mean, m2} */
+  float* dw;                /* (N_out, K) contiguous, every element written; NULL: not wanted */
+  float* db;                /* N_out, every element written; NULL: not wanted */
+} GhXfWgrad;
+
+/* The gradients' buffers: GhXfStem's and GhXfLayer's fields, each NULL (not wanted, never written) or a contiguous buffer of the
+ * parameter's shape; qkv1 and qkv2 are the stacked (3M, M) gradients of [Wq; Wk; Wv]. */
+typedef struct GhXfStemG {
+  float *gn_w, *gn_b;
+  float *in_w, *in_b;
+  float *out_w, *out_b;
+} GhXfStemG;
+
+typedef struct GhXfLayerG {
+  float *ln1_w, *ln1_b;
+  float* qkv1;
+  float *o1_w, *o1_b;
+  float *ln2_w, *ln2_b;
+  float* qkv2;
+  float *o2_w, *o2_b;
+  float *ln3_w, *ln3_b;
+  float *ff1_w, *ff1_b;
+  float *ff2_w, *ff2_b;
+} GhXfLayerG;
+
+/* Rows per chunk of the backward-weight product (0 for invalid sizes), and the bytes of its partials (0 with one chunk). */
+int gh_xf_linear_wgrad_chunk(int T, int K, int N_out);
+size_t gh_xf_linear_wgrad_workspace_bytes(int T, int K, int N_out);
+int gh_xf_linear_wgrad(const GhXfWgrad* args, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* dgamma, dbeta (K) of a LayerNorm whose output's cotangent is dn (T, K), at x (T, K) with moments (T, 2) {mean, rstd}; either may be
+ * NULL; any K >= 1. */
+size_t gh_xf_layernorm_param_grads_workspace_bytes(int T, int K);
+int gh_xf_layernorm_param_grads(const float* dn, int64_t dn_stride, const float* x, int64_t x_stride, const float* moments, int T, int K,
+                                float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* dgamma, dbeta (C) of the GroupNorm whose output's cotangent is dy; dy, x (B, C, N) contiguous, moments (B, G, 2) {mean, m2}. */
+size_t gh_xf_group_norm_param_grads_workspace_bytes(int B, int C, int N, int G);
+int gh_xf_group_norm_param_grads(const float* dy, const float* x, const float* moments, int B, int C, int N, int G, float eps,
+                                 float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* gh_xf_backward plus the gradient of every parameter gstem / glayers name. fstem / flayers: the weights as gh_xf_forward_tape read
+ * them. dx may be NULL. Sizes are gh_xf_backward's. */
+size_t gh_xf_backward_params_workspace_bytes(const GhXfDims* dims);
+int gh_xf_backward_params(const GhXfDims* dims, const GhXfStemT* stem, const GhXfLayerT* layers, const GhXfStem* fstem,
+                          const GhXfLayer* flayers, const GhXfStemG* gstem, const GhXfLayerG* glayers, const float* x, const void* tape,
+                          const float* dout, float* dx, void* workspace, size_t ws_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
