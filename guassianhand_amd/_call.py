@@ -1,5 +1,6 @@
 """What the Python wrappers of the C-ABI share: the loaded library, the ctypes forms of tensors and streams, the rows-in-place rule,
-the host-side argument checks, the null-cotangent rule and the one way an entry point is called. _raster_launch.py keeps wrappers of its own (its pointers are plain
+the host-side argument checks, the padded row count and the device test of the convolution blocks (perceptual.py, lpips.py), the
+null-cotangent rule and the one way an entry point is called. _raster_launch.py keeps wrappers of its own (its pointers are plain
 integers for struct fields, and its stream and device handling were tuned for the render loop)."""
 from __future__ import annotations
 
@@ -51,6 +52,16 @@ def check_f32(x: torch.Tensor, named) -> None:
             raise ValueError(f"{name}: expected {nd} dimensions, got {tuple(t.shape)}")
         if t.device != x.device:
             raise ValueError(f"{name} is on {t.device}, x on {x.device}")
+
+
+def pad_to(c: int, chunk: int) -> int:
+    """c rounded up to a multiple of `chunk`: the rows of a packed convolution weight (GH_CONV_CHUNK, GH_LPIPS_CHUNK)."""
+    return -(-c // chunk) * chunk
+
+
+def on_device(x) -> bool:
+    """A float32 (N, H, W, C) tensor on a ROCm device: what the convolution, pooling and LPIPS kernels read."""
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
 
 
 def check_ops(ops: str) -> None:

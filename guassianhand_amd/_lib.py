@@ -37,7 +37,8 @@ HEADERS = ("gh_internal.h", os.path.join("..", "..", "include", "gh_raster.h"), 
            os.path.join("..", "..", "include", "gh_trunk.h"), os.path.join("..", "..", "include", "gh_conv.h"),
            os.path.join("..", "..", "include", "gh_mano.h"), os.path.join("..", "..", "include", "gh_xf.h"),
            os.path.join("..", "..", "include", "gh_lpips.h"),
-           os.path.join("..", "csrc_rows", "gh_rows.h"), os.path.join("..", "csrc_head", "gh_head_act.h"))
+           os.path.join("..", "csrc_rows", "gh_rows.h"), os.path.join("..", "csrc_head", "gh_head_act.h"),
+           os.path.join("..", "csrc_conv", "gh_conv_tile.h"))
 # -ffp-contract=off: FMAs only where the source says fmaf() (arithmetic contract)
 # -fno-slp-vectorize: keeps the DPP butterflies as v_add_f32_dpp instead of v_mov_dpp + v_pk_add_f32
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17")

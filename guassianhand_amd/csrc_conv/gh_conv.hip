@@ -7,12 +7,13 @@
 // The product is gh_rows.h's "columns" form: the pixel is the column of v_mfma_f32_32x32x2_f32, a wave owns 32 pixels, an accumulator
 // 32 output channels, and the weights (the A operand) cross LDS in slabs of (32 NH) x 32 that the four waves share. Unlike ghr_mm_x a
 // lane takes the 16 CONSECUTIVE channels 16 half .. 16 half + 15 of a slab as its B operands (four 16-byte loads), so step s of a
-// slab multiplies the channels s and 16 + s: the order include/gh_conv.h states.
+// slab multiplies the channels s and 16 + s: the order include/gh_conv.h states. csrc_conv/gh_conv_tile.h holds the host's launch
+// rules, which gh_lpips.hip's convolution shares.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gh_conv.h"
-#include "../csrc_rows/gh_rows.h"
+#include "gh_conv_tile.h"
 
 #define GC_T32(c) (((c) + 31) / 32)
 
@@ -127,18 +128,11 @@ __global__ __launch_bounds__(GHR_BLOCK) void gc_conv_kernel(GcArgs a) {
   }
 }
 
-static int gc_auto_chunk(long long tiles, int CoP) {
-  for (int ch = GH_CONV_CHUNK; ch > 32; ch /= 2) {
-    if (tiles * (CoP / ch) >= GH_CONV_FILL) return ch;
-  }
-  return 32;
-}
-
 // The checks both directions share, and the launch. Ci / Co are the product's input and output channel counts.
 static int gc_conv(const float* in, const uint32_t* gate, int N, int H, int W, int Ci, int Co, const float* w, const float* bias,
                    uint32_t flags, int chunk, float* out, uint32_t* gate_out, bool gated, void* hip_stream) {
   if (N < 0 || H < 0 || W < 0 || Ci < 1 || Co < 1 || (flags & ~(uint32_t)GH_CONV_RELU)) return GH_ERR_INVALID_ARG;
-  if (chunk != 0 && chunk != 32 && chunk != 64 && chunk != 128) return GH_ERR_INVALID_ARG;
+  if (!gct_chunk_ok(chunk)) return GH_ERR_INVALID_ARG;
   if (Ci > GH_CONV_MAX_C || Co > GH_CONV_MAX_C) return GH_ERR_UNSUPPORTED;
   const long long NP = (long long)N * H * W;
   const long long tiles = (NP + GH_CONV_PIXELS - 1) / GH_CONV_PIXELS;
@@ -151,18 +145,15 @@ static int gc_conv(const float* in, const uint32_t* gate, int N, int H, int W, i
   a.in = in; a.gate = (gated && relu) ? gate : nullptr; a.w = w; a.bias = bias; a.out = out;
   a.gate_out = (!gated && relu) ? (uint16_t*)gate_out : nullptr;
   a.NP = NP; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.CoP = gc_pad(Co); a.relu = (!gated && relu) ? 1 : 0;
-  a.vec_w = (ghr_al16(w) && Ci % 4 == 0) ? 1 : 0;
-  a.vec_in = (ghr_al16(in) && Ci % 4 == 0) ? 1 : 0;
-  a.vec_out = (ghr_al16(out) && Co % 4 == 0) ? 1 : 0;
-  if (chunk == 0) chunk = gc_auto_chunk(tiles, a.CoP);
-  const int nh = chunk / 32;
+  gct_vec(a, Ci % 4 == 0);
+  if (chunk == 0) chunk = gct_auto_chunk(tiles, a.CoP, GH_CONV_CHUNK, GH_CONV_FILL);
   const dim3 grid((unsigned)tiles, (unsigned)((Co + chunk - 1) / chunk));
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();
-  const bool g = a.gate != nullptr;
-  if (nh == 4) { if (g) hipLaunchKernelGGL((gc_conv_kernel<4, true>), grid, dim3(GHR_BLOCK), 0, st, a); else hipLaunchKernelGGL((gc_conv_kernel<4, false>), grid, dim3(GHR_BLOCK), 0, st, a); }
-  else if (nh == 2) { if (g) hipLaunchKernelGGL((gc_conv_kernel<2, true>), grid, dim3(GHR_BLOCK), 0, st, a); else hipLaunchKernelGGL((gc_conv_kernel<2, false>), grid, dim3(GHR_BLOCK), 0, st, a); }
-  else { if (g) hipLaunchKernelGGL((gc_conv_kernel<1, true>), grid, dim3(GHR_BLOCK), 0, st, a); else hipLaunchKernelGGL((gc_conv_kernel<1, false>), grid, dim3(GHR_BLOCK), 0, st, a); }
+  gct_nh(chunk, [&](auto nh) {
+    if (a.gate) hipLaunchKernelGGL((gc_conv_kernel<nh(), true>), grid, dim3(GHR_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((gc_conv_kernel<nh(), false>), grid, dim3(GHR_BLOCK), 0, st, a);
+  });
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
 }
 

@@ -12,7 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/gh_lpips.h"
-#include "../csrc_rows/gh_rows.h"
+#include "../csrc_conv/gh_conv_tile.h"
 
 static inline int gl_pad(int c) { return (c + GH_LPIPS_CHUNK - 1) / GH_LPIPS_CHUNK * GH_LPIPS_CHUNK; }
 static inline int gl_out(int H, int K, int s, int p) { return H + 2 * p < K ? 0 : (H + 2 * p - K) / s + 1; }
@@ -148,29 +148,15 @@ __global__ __launch_bounds__(GHR_BLOCK) void gl_conv_kernel(GlConvArgs a) {
   }
 }
 
-static int gl_auto_chunk(long long tiles, int CoP) {
-  for (int ch = GH_LPIPS_CHUNK; ch > 32; ch /= 2) {
-    if (tiles * (CoP / ch) >= GH_LPIPS_FILL) return ch;
-  }
-  return 32;
-}
-
 // the header's first two groups of checks; *NP receives the number of output pixels
 static int gl_conv_sizes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad, uint32_t flags, int chunk, long long* NP) {
   if (N < 0 || H < 0 || W < 0 || Cin < 1 || Cout < 1) return GH_ERR_INVALID_ARG;
   if ((K != 3 && K != 5 && K != 11) || (stride != 1 && stride != 4) || pad < 0 || pad >= K) return GH_ERR_INVALID_ARG;
-  if ((flags & ~(uint32_t)GH_LPIPS_RELU) || (chunk != 0 && chunk != 32 && chunk != 64 && chunk != 128)) return GH_ERR_INVALID_ARG;
+  if ((flags & ~(uint32_t)GH_LPIPS_RELU) || !gct_chunk_ok(chunk)) return GH_ERR_INVALID_ARG;
   if (Cin > GH_LPIPS_MAX_C || Cout > GH_LPIPS_MAX_C) return GH_ERR_UNSUPPORTED;
   *NP = (long long)N * gl_out(H, K, stride, pad) * gl_out(W, K, stride, pad);
   if ((*NP + GH_LPIPS_PIXELS - 1) / GH_LPIPS_PIXELS > 2147483647LL) return GH_ERR_UNSUPPORTED;
   return GH_OK;
-}
-
-template <bool FLAT>
-static void gl_conv_launch(int nh, dim3 grid, hipStream_t st, const GlConvArgs& a) {
-  if (nh == 4) hipLaunchKernelGGL((gl_conv_kernel<4, FLAT>), grid, dim3(GHR_BLOCK), 0, st, a);
-  else if (nh == 2) hipLaunchKernelGGL((gl_conv_kernel<2, FLAT>), grid, dim3(GHR_BLOCK), 0, st, a);
-  else hipLaunchKernelGGL((gl_conv_kernel<1, FLAT>), grid, dim3(GHR_BLOCK), 0, st, a);
 }
 
 extern "C" size_t gh_conv2d_weight_floats(int Cin, int Cout, int K) {
@@ -191,16 +177,16 @@ extern "C" int gh_conv2d_forward(const float* x, int N, int H, int W, int Cin, i
   a.H = H; a.W = W; a.Ho = gl_out(H, K, stride, pad); a.Wo = gl_out(W, K, stride, pad);
   a.Ci = Cin; a.Co = Cout; a.CoP = gl_pad(Cout); a.K = K; a.stride = stride; a.pad = pad;
   a.R = K * K * Cin; a.Rp = (a.R + 3) / 4 * 4; a.relu = (flags & GH_LPIPS_RELU) ? 1 : 0;
-  a.vec_w = (ghr_al16(wp) && (flat || Cin % 4 == 0)) ? 1 : 0;        // a slab starts at a multiple of 4 floats of a row of Rp
-  a.vec_in = (ghr_al16(x) && Cin % 4 == 0) ? 1 : 0;
-  a.vec_out = (ghr_al16(y) && Cout % 4 == 0) ? 1 : 0;
+  gct_vec(a, flat || Cin % 4 == 0);                                 // a slab starts at a multiple of 4 floats of a row of Rp
   const long long tiles = (NP + GH_LPIPS_PIXELS - 1) / GH_LPIPS_PIXELS;
-  if (chunk == 0) chunk = gl_auto_chunk(tiles, a.CoP);
+  if (chunk == 0) chunk = gct_auto_chunk(tiles, a.CoP, GH_LPIPS_CHUNK, GH_LPIPS_FILL);
   const dim3 grid((unsigned)tiles, (unsigned)((Cout + chunk - 1) / chunk));
   hipStream_t st = (hipStream_t)hip_stream;
   (void)hipGetLastError();
-  if (flat) gl_conv_launch<true>(chunk / 32, grid, st, a);
-  else gl_conv_launch<false>(chunk / 32, grid, st, a);
+  gct_nh(chunk, [&](auto nh) {
+    if (flat) hipLaunchKernelGGL((gl_conv_kernel<nh(), true>), grid, dim3(GHR_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((gl_conv_kernel<nh(), false>), grid, dim3(GHR_BLOCK), 0, st, a);
+  });
   return hipGetLastError() == hipSuccess ? GH_OK : GH_ERR_LAUNCH;
 }
 

@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
-from ._call import check_ops, launch, lib, ptr, workspace
+from ._call import check_ops, launch, lib, on_device, pad_to, ptr, workspace
 
 MIN_SIZE = _abi.GH_LPIPS_MIN_SIZE
 MAX_C = _abi.GH_LPIPS_MAX_C
@@ -45,26 +45,18 @@ CONVS = ((0, 11, 4, 2, False), (3, 5, 1, 2, True), (6, 3, 1, 1, True), (8, 3, 1,
 SHIFT, SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)
 
 
-def _pad(c: int) -> int:
-    return -(-c // _abi.GH_LPIPS_CHUNK) * _abi.GH_LPIPS_CHUNK
-
-
 def pack_conv(weight: torch.Tensor) -> torch.Tensor:
     """wp of include/gh_lpips.h from a (Cout, Cin, K, K) weight: (pad(Cout), Rp) with wp[co][(K ky + kx) Cin + ci] = W[co][ci][ky][kx],
     R = K K Cin rounded up to a multiple of 4; the padding rows and columns are zeros."""
     w = weight.detach().float()
     Cout, Cin, K, _ = w.shape
     R = K * K * Cin
-    wp = w.new_zeros(_pad(Cout), -(-R // 4) * 4)
+    wp = w.new_zeros(pad_to(Cout, _abi.GH_LPIPS_CHUNK), -(-R // 4) * 4)
     wp[:Cout, :R] = w.permute(0, 2, 3, 1).reshape(Cout, R)
     return wp
 
 
 # ---- the single kernels (channels-last) ---------------------------------------------------------------------------------------------------
-def _on_device(x) -> bool:
-    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-
-
 def _check_on(dev, named) -> None:
     """Every (name, tensor, dtype) a launch would read is a tensor of that dtype on `dev` (None passes), or the call is refused on the
     host with a ValueError before anything is launched: a kernel handed a host address faults the device."""
@@ -93,7 +85,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     for ops="torch" and for everything else torch takes. `packed` is pack_conv(weight) where the caller keeps it; `chunk`
     (0, 32, 64, 128) fixes the kernel's chunk of output channels, which no result depends on."""
     check_ops(ops)
-    if ops != "fused" or not _on_device(x):
+    if ops != "fused" or not on_device(x):
         return conv2d_ref(x, weight, bias, stride, padding, relu)
     Cout, Cin, K, K2 = weight.shape
     if K != K2 or x.shape[3] != Cin:
@@ -101,7 +93,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     _check_on(x.device, (("weight", weight, torch.float32), ("bias", bias, torch.float32), ("packed", packed, torch.float32)))
     if bias is not None and tuple(bias.shape) != (Cout,):
         raise ValueError(f"conv2d: bias {tuple(bias.shape)} does not fit the weight {tuple(weight.shape)}")
-    if packed is not None and packed.numel() != _pad(Cout) * (-(-K * K * Cin // 4) * 4):
+    if packed is not None and packed.numel() != pad_to(Cout, _abi.GH_LPIPS_CHUNK) * (-(-K * K * Cin // 4) * 4):
         raise ValueError(f"conv2d: packed {tuple(packed.shape)} is not pack_conv of a weight {tuple(weight.shape)}")
     x = x.detach().contiguous()
     wp = pack_conv(weight) if packed is None else packed.contiguous()
@@ -117,7 +109,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 def max_pool3x3s2(x: torch.Tensor, ops: str = "fused") -> torch.Tensor:
     """x (N, H, W, C) -> (N, Ho, Wo, C): F.max_pool2d(kernel 3, stride 2) channels-last."""
     check_ops(ops)
-    if ops != "fused" or not _on_device(x):
+    if ops != "fused" or not on_device(x):
         return F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2).permute(0, 2, 3, 1)
     x = x.detach().contiguous()
     N, H, W, Cn = x.shape
@@ -139,7 +131,7 @@ def lpips_layer_ref(f: torch.Tensor, lin: torch.Tensor, acc: Optional[torch.dtyp
 def lpips_layer(f: torch.Tensor, lin: torch.Tensor, ops: str = "fused") -> torch.Tensor:
     """d_l of a (2N, h, w, C) map and a (C,) `lin` weight: (N,) float64 (gh_lpips_layer on a float32 ROCm tensor)."""
     check_ops(ops)
-    if ops != "fused" or not _on_device(f):
+    if ops != "fused" or not on_device(f):
         return lpips_layer_ref(f, lin).double()
     _check_on(f.device, (("lin", lin, torch.float32),))
     if f.shape[0] % 2 or tuple(lin.shape) != (f.shape[3],):
@@ -327,7 +319,7 @@ def _forward_fused(net: AlexLPIPS, x: torch.Tensor, N: int, want_terms: bool):
     dev = x.device
     _check_net(net, dev)
     _check_on(dev, [(name, t, torch.float32) for name, t in _net_tensors(net)])
-    if not _on_device(x) or x.shape[0] != 2 * N or x.shape[3] != 3:
+    if not on_device(x) or x.shape[0] != 2 * N or x.shape[3] != 3:
         raise ValueError(f"expected a prepared (2N, h, w, 3) float32 input on a ROCm device, got {tuple(x.shape)}")
     x = x.contiguous()
     h, w = x.shape[1], x.shape[2]

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _abi
-from ._call import check_ops, cotangent, launch, ptr
+from ._call import check_ops, cotangent, launch, on_device, pad_to, ptr
 
 MAX_C = _abi.GH_CONV_MAX_C
 # (slice, torchvision features index, input width, output width) with widths as indices into (3,) + widths
@@ -45,18 +45,14 @@ TAP_WEIGHTS = (1.0 / 16, 1.0 / 8, 1.0 / 4, 1.0)
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
-def _pad(c: int) -> int:
-    return -(-c // _abi.GH_CONV_CHUNK) * _abi.GH_CONV_CHUNK
-
-
 def pack_weights(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(wf, wb) of include/gh_conv.h from a (Cout, Cin, 3, 3) weight: wf (9, pad(Cout), Cin) tap-major, wb (9, pad(Cin), Cout) the
     flipped, transposed layout of the backward-data product; the padding rows are zeros."""
     w = weight.detach().float()
     Cout, Cin = w.shape[:2]
-    wf = w.new_zeros(9, _pad(Cout), Cin)
+    wf = w.new_zeros(9, pad_to(Cout, _abi.GH_CONV_CHUNK), Cin)
     wf[:, :Cout] = w.permute(2, 3, 0, 1).reshape(9, Cout, Cin)
-    wb = w.new_zeros(9, _pad(Cin), Cout)
+    wb = w.new_zeros(9, pad_to(Cin, _abi.GH_CONV_CHUNK), Cout)
     wb[:, :Cin] = w.flip(2, 3).permute(2, 3, 1, 0).reshape(9, Cin, Cout)
     return wf, wb
 
@@ -144,13 +140,9 @@ class _MaxPool2x2Fn(torch.autograd.Function):
         return _pool_backward(cotangent(gy), choice, *ctx.hw)
 
 
-def _on_device(x: torch.Tensor) -> bool:
-    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-
-
 def _conv_applies(x, weight, bias) -> bool:
     """The conditions of the module docstring on every tensor the kernels would read."""
-    if not _on_device(x) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.shape[3] != weight.shape[1]:
+    if not on_device(x) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.shape[3] != weight.shape[1]:
         return False
     params = [weight] + ([] if bias is None else [bias])
     if any(p.requires_grad or p.dtype != torch.float32 or p.device != x.device for p in params):
@@ -177,7 +169,7 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
 def max_pool2x2(x: torch.Tensor, ops: str = "fused") -> torch.Tensor:
     """x (N, H, W, C) -> (N, H/2, W/2, C): F.max_pool2d(kernel 2, stride 2) channels-last. Differentiable in x."""
     check_ops(ops)
-    if ops != "fused" or not _on_device(x) or x.shape[3] < 1:
+    if ops != "fused" or not on_device(x) or x.shape[3] < 1:
         return max_pool2x2_ref(x)
     return _MaxPool2x2Fn.apply(x)
 
@@ -185,7 +177,7 @@ def max_pool2x2(x: torch.Tensor, ops: str = "fused") -> torch.Tensor:
 def feature_distance(f: torch.Tensor, t: torch.Tensor, *, ops: str = "fused") -> torch.Tensor:
     """mean|f - t|, differentiable in f (sign(f - t) / n, sign(0) = 0): gh_l1_loss where the kernels apply."""
     check_ops(ops)
-    if ops == "fused" and _on_device(f) and _on_device(t) and f.shape == t.shape and f.numel() > 0 and not t.requires_grad:
+    if ops == "fused" and on_device(f) and on_device(t) and f.shape == t.shape and f.numel() > 0 and not t.requires_grad:
         from .loss import l1_mean_loss
         return l1_mean_loss(f, t)
     return (f - t).abs().mean()

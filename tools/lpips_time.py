@@ -89,9 +89,11 @@ def main():
             xin, packed = torch.randn(2 * Nv, h, w, ci, device=dev), LP.pack_conv(conv.weight)
             run = lambda: LP.conv2d(xin, conv.weight, conv.bias, s, p, relu=True, packed=packed)
             run()
-            t = statistics.median(timed(run, args.iters) for _ in range(args.repeat))
+            win = [timed(run, args.iters) for _ in range(args.repeat)]
+            t = statistics.median(win)
             fl = 2 * K * K * ci * co * 2 * Nv * ho * wo
-            say(f"    conv{k} {ci:3d} -> {co:3d} k{K:<2d} s{s} at {h:4d}x{w:<4d} -> {ho:3d}x{wo:<3d}  {t:8.3f} ms {fl / t / 1e9:6.1f} TFLOP/s")
+            say(f"    conv{k} {ci:3d} -> {co:3d} k{K:<2d} s{s} at {h:4d}x{w:<4d} -> {ho:3d}x{wo:<3d}  {t:8.3f} ms [{min(win):.3f} .. {max(win):.3f}] "
+                f"{fl / t / 1e9:6.1f} TFLOP/s")
         say()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:

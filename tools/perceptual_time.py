@@ -103,11 +103,12 @@ def main():
             wf, wb = P.pack_weights(conv.weight)
             _, gate = P._conv_forward(xin, wf, conv.bias, Cout, True)
             P._conv_backward(g, gate, wb, Cin, True)
-            tf = statistics.median(timed(lambda: P._conv_forward(xin, wf, conv.bias, Cout, True), args.iters) for _ in range(args.repeat))
-            tb = statistics.median(timed(lambda: P._conv_backward(g, gate, wb, Cin, True), args.iters) for _ in range(args.repeat))
+            wf_ = [timed(lambda: P._conv_forward(xin, wf, conv.bias, Cout, True), args.iters) for _ in range(args.repeat)]
+            wb_ = [timed(lambda: P._conv_backward(g, gate, wb, Cin, True), args.iters) for _ in range(args.repeat)]
+            tf, tb = statistics.median(wf_), statistics.median(wb_)
             fl = 2 * 9 * Cin * Cout * B * h * w
-            say(f"    features.{n:<2d} {Cin:3d} -> {Cout:3d} at {h:3d}x{w:<3d}  forward {tf:7.3f} ms {fl / tf / 1e9:6.1f} TFLOP/s   "
-                f"backward-data {tb:7.3f} ms {fl / tb / 1e9:6.1f} TFLOP/s")
+            say(f"    features.{n:<2d} {Cin:3d} -> {Cout:3d} at {h:3d}x{w:<3d}  forward {tf:7.3f} ms [{min(wf_):.3f} .. {max(wf_):.3f}] "
+                f"{fl / tf / 1e9:6.1f} TFLOP/s   backward-data {tb:7.3f} ms [{min(wb_):.3f} .. {max(wb_):.3f}] {fl / tb / 1e9:6.1f} TFLOP/s")
         say()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
