@@ -133,22 +133,31 @@ __device__ __forceinline__ float ghr_sum4(const float* s_red, int lane) {
 struct GhrMoments { float mean, m2; };  // m2: the sum of the squared deviations from the mean
 
 // the moments of the n columns of the lane's row vr: wave w sums the columns k = w mod 4 in ascending order, the four shares are added
-// by ghr_sum4. s_red is 2 x GHR_BLOCK floats (one half per pass); two barriers, so every thread of the workgroup calls it.
+// by ghr_sum4. The first pass's mean carries the rounding of a sum of n values, a few ulp of the mean itself — all of the deviation of a
+// row whose mean dwarfs it — so the second pass also sums the deviations from it: their mean corrects the first, and m2 is taken about
+// the corrected mean (sum d^2 - (sum d)^2 / n). s_red is 2 x GHR_BLOCK floats; three barriers, so every thread of the workgroup calls it.
+// Its last reads touch both halves of s_red: a caller puts a barrier before it writes either half again.
 __device__ __forceinline__ GhrMoments ghr_moments(const float* vr, int n, float* s_red, int lane, int wave) {
   GhrMoments r;
   float s = 0.f;
   for (int k = wave; k < n; k += 4) s += vr[k];
   s_red[wave * GHR_ROWS + lane] = s;
   __syncthreads();
-  r.mean = ghr_sum4(s_red, lane) / (float)n;
-  float q = 0.f;
+  const float mean = ghr_sum4(s_red, lane) / (float)n;
+  float q = 0.f, e = 0.f;
   for (int k = wave; k < n; k += 4) {
-    const float d = vr[k] - r.mean;
+    const float d = vr[k] - mean;
+    e += d;
     q = fmaf(d, d, q);
   }
   s_red[GHR_BLOCK + wave * GHR_ROWS + lane] = q;
+  __syncthreads();  // (every read of the first half lies before this barrier: it is free for the deviations' sums)
+  s_red[wave * GHR_ROWS + lane] = e;
   __syncthreads();
-  r.m2 = ghr_sum4(s_red + GHR_BLOCK, lane);
+  const float es = ghr_sum4(s_red, lane), c = es / (float)n;
+  r.mean = mean + c;
+  const float m2 = fmaf(-es, c, ghr_sum4(s_red + GHR_BLOCK, lane));
+  r.m2 = m2 < 0.f ? 0.f : m2;  // (the difference can round below 0 where every deviation is the same; a NaN stays)
   return r;
 }
 

@@ -36,7 +36,7 @@ struct GtAct {  // what a product applies to its source on the way: the activati
 };
 // d * act'(v)
 __device__ __forceinline__ float gt_dact(float v, float d, bool relu) {
-  if (relu) return v > 0.f ? d : 0.f;
+  if (relu) return v > 0.f ? d : (v == v ? 0.f : v);  // (a NaN pre-activation reaches the gradient, as it reaches the output)
   const float s = ghr_sigmoid(v);
   return d * (s * (1.0f + v * (1.0f - s)));
 }

@@ -26,8 +26,9 @@
  *
  * Arithmetic (float32 throughout, -ffp-contract=off: FMAs only where stated). One 4-wave workgroup works on 64 rows, lane = row,
  * weights wave-uniform (32 rows, every row on two lanes, where the tile of 64 would not fit 128 KiB of LDS; the values are the same).
- *   moments    both LayerNorms: the mean, then the centred sum of squares (one fmaf per term), each as four partial sums over the
- *              columns k mod 4 in ascending k, added as (s0 + s1) + (s2 + s3); biased variance; rstd = 1 / sqrtf(m2 / F + eps);
+ *   moments    both LayerNorms: the mean, then the deviations' sum and the centred sum of squares (one fmaf per term), each as four
+ *              partial sums over the columns k mod 4 in ascending k, added as (s0 + s1) + (s2 + s3); the mean is corrected by the
+ *              deviations' mean c (mean + c, m2 = sum d^2 - c sum d, not below 0); biased variance; rstd = 1 / sqrtf(m2 / F + eps);
  *              xhat = (x - mean) * rstd, xn = fmaf(xhat, weight, bias). The backward recomputes xhat from the saved mean and rstd.
  *   forward    a dot product W[j, :] . in is four partial sums (k mod 4), one fmaf per term in ascending k, ((s0 + s1) + (s2 + s3)) +
  *              bias. The residuals add as written above: x + (dot + bias), y + (dot + bias).

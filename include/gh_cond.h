@@ -27,7 +27,7 @@
  *     Layout in floats: c0 at 0, W1g at Hd, batch element b at Hd + Hd*Dv + b*(2 + 2*Hd) as m_e, M_e, c1[Hd], c2[Hd].
  *
  *   forward, per row:
- *     m_v = mean(v), M_v = sum (v - m_v)^2          two passes over the row
+ *     m_v = mean(v), M_v = sum (v - m_v)^2          two passes over the row, m_v corrected by the mean of the second pass's deviations
  *     delta = m_e - m_v      mu = fmaf(delta, De/D, m_v)      M = (M_v + M_e) + (delta * delta) * (Dv*De/D)     (the pairwise form)
  *     rstd = 1 / sqrt(M / D + eps)                  correctly rounded division and square root
  *     pre1 = fmaf(rstd, (W1g . (v - mu) + c2) + (m_e - mu) * c1, c0)         h1 = relu(pre1), a NaN passes

@@ -12,7 +12,8 @@
  *
  * and the five outputs are gh_head.h's activations of raw[p] and pts[p], formula for formula (the GhHeadDesc is gh_head.h's).
  *   GH_TRUNK_SILU   act(v) = v / (1 + exp(-v));    act'(v) = s (1 + v (1 - s)) with s = 1 / (1 + exp(-v))
- *   GH_TRUNK_RELU   act(v) = 0 for v < 0, else v (a NaN passes);    act'(v) = 1 for v > 0, else 0
+ *   GH_TRUNK_RELU   act(v) = 0 for v < 0, else v (a NaN passes);    act'(v) = 1 for v > 0, else 0 (a NaN v makes the
+ *                   gradient NaN, as it makes the output)
  *
  * Backward, for frozen weights: with graw the gradient of raw under gh_head.h's backward formulas (trunc_exp's clamp at 15, the clip
  * gate, F.normalize's floor, sigmoid), read from the forward's `raw`,

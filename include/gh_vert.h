@@ -7,7 +7,7 @@
  * division), per row:
  *
  *     z    = (x[p, 0..Cf), pts[p, 0..3))                                         never written anywhere
- *     zn   = LayerNorm(z) * ln_weight + ln_bias     mean, then the CENTRED sum of squares; biased variance; rstd = 1 / sqrt(var + eps)
+ *     zn   = LayerNorm(z) * ln_weight + ln_bias     mean (corrected by the mean of the deviations from it), then the CENTRED sum of squares; biased variance; rstd = 1 / sqrt(var + eps)
  *     h1   = relu(fc1_weight (Hd, D) . zn + fc1_bias)
  *     h2   = fc2_weight (Hd, Hd) . h1 + fc2_bias
  *     o    = fc_weight (K, Hd) . h2 + fc_bias

@@ -65,18 +65,24 @@ def run(c, mode, used=FIELDS, x=None):
     return out
 
 
-def margins(c):
-    """(ReLU: min over v1, v2 of min|v| / max|v| and whether both signs occur; clip: min|exp(raw) - clip| / max exp(raw) and whether
-    both sides occur) in float64; None where the case has no such kink."""
+def layers64(c):
+    """(v1, v2, y) in float64: the two hidden pre-activations and the trunk's output, as the statements give them."""
     W1, b1, W2, b2, W3, b3 = (t.double() for t in c.trunk)
     act = F.relu if c.kw["activation"] == "relu" else F.silu
     v1 = F.linear(c.x.double(), W1, b1)
     v2 = F.linear(act(v1), W2, b2)
+    return v1, v2, F.linear(act(v2), W3, b3)
+
+
+def margins(c):
+    """(ReLU: min over v1, v2 of min|v| / max|v| and whether both signs occur; clip: min|exp(raw) - clip| / max exp(raw) and whether
+    both sides occur) in float64; None where the case has no such kink."""
+    v1, v2, y = layers64(c)
     relu = clip = None
     if c.kw["activation"] == "relu":
         relu = (min(float(v.abs().min() / v.abs().max()) for v in (v1, v2)), all(bool((v > 0).any() and (v < 0).any()) for v in (v1, v2)))
     if c.kw["clip_scaling"] is not None:
-        s = torch.exp(F.linear(F.linear(act(v2), W3, b3), c.Wh.double()[3:6], c.bh.double()[3:6]))
+        s = torch.exp(F.linear(y, c.Wh.double()[3:6], c.bh.double()[3:6]))
         t = c.kw["clip_scaling"]
         clip = (float((s - t).abs().min() / s.abs().max()), bool((s > t).any() and (s < t).any()))
     return relu, clip
