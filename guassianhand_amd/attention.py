@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_ops, launch, lib, ptr, workspace
 
 HEAD_DIM = _abi.GH_ATTN_D
@@ -226,22 +226,19 @@ class SelfAttn(nn.Module):
         return self.ff(x)
 
 
-_fused_cls = {}
+_SEAM = (__name__, "fused_self_attn_cls")
 
 
 def fused_self_attn_cls(base):
     """A subclass of the given class (the reference's own tgs.models.self_attn.SelfAttn) whose self_attn(x) is self_attn_core while
     the attention dropouts are inactive, and the base class's own self_attn, unchanged, in train mode with p > 0. forward stays
     the base class's."""
-    if base not in _fused_cls:
-        def self_attn(self, x):
-            if _attn_dropout_active(self):
-                return base.self_attn(self, x)
-            return self_attn_core(self, x)
+    def self_attn(self, x):
+        if _attn_dropout_active(self):
+            return base.self_attn(self, x)
+        return self_attn_core(self, x)
 
-        _fused_cls[base] = type(base.__name__, (base,), {"self_attn": self_attn, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X attention core"})
-    return _fused_cls[base]
+    return _seam.graft(_SEAM, base, {"self_attn": self_attn}, "attention core")
 
 
 def fuse_self_attn(renderer):
@@ -249,6 +246,6 @@ def fuse_self_attn(renderer):
     points then runs the HIP attention core. The module object, its parameters and its state dict are untouched; it may be called on
     a renderer that is already built, and again. Returns the renderer."""
     m = renderer.self_attn_layer
-    if type(m) not in _fused_cls.values() and not isinstance(m, SelfAttn):
-        m.__class__ = fused_self_attn_cls(type(m))
+    if not isinstance(m, SelfAttn):
+        _seam.swap(_SEAM, m)
     return renderer

@@ -39,7 +39,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_ops, launch, lib, ptr, struct, workspace
 from .attention import HEAD_DIM, attention_ref
 
@@ -344,25 +344,20 @@ def _block_forward(self, x: torch.Tensor, before):
     return _run(x, None, [(0, BS, V)] if BS * V > 0 else [], P, n_heads, eps, norm, None)
 
 
-_fused_cls = {}
+_SEAM = (__name__, "fused_attn_block_cls")
 
 
 def fused_attn_block_cls(base):
     """A subclass of the given SelfAttn class (the reference's own, or what fuse_self_attn made of it) whose forward(x) is the fused
     block while the kernels apply, and the given class's own forward, unchanged, otherwise."""
-    if base not in _fused_cls:
-        def forward(self, x):
-            return _block_forward(self, x, base.forward)
+    def forward(self, x):
+        return _block_forward(self, x, base.forward)
 
-        _fused_cls[base] = type(base.__name__, (base,), {"forward": forward, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X attention block"})
-    return _fused_cls[base]
+    return _seam.graft(_SEAM, base, {"forward": forward}, "attention block")
 
 
 def fuse_attn_block(renderer):
     """Swap the class of `renderer.self_attn_layer` for fused_attn_block_cls of its own class. The module object, its parameters and
     its state dict are untouched; it may be called on a renderer that is already built, and again. Returns the renderer."""
-    m = renderer.self_attn_layer
-    if type(m) not in _fused_cls.values():
-        m.__class__ = fused_attn_block_cls(type(m))
+    _seam.swap(_SEAM, renderer.self_attn_layer)
     return renderer

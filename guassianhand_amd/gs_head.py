@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_f32, check_ops, cotangent, launch, lib, ptr, row_stride, rows, workspace
 from .renderer import GaussianModel, gs_activations
 
@@ -257,27 +257,23 @@ class GSLayer(nn.Module):
         return gs_layer_forward(self, x, pts)
 
 
-_fused_cls = {}
+_SEAM = (__name__, "fused_gs_layer_cls")
 
 
 def is_fused_cls(cls) -> bool:
-    return cls in _fused_cls.values()
+    return _seam.is_grafted(_SEAM, cls)
 
 
 def fused_gs_layer_cls(base):
     """A subclass of the given GSLayer class (the reference's own, tgs.models.renderer_one_shot.GSLayer) whose forward is
     gs_layer_forward; configure(), the parameters and the config handling stay the base class's."""
-    if base not in _fused_cls:
-        _fused_cls[base] = type(base.__name__, (base,), {"forward": lambda self, x, pts: gs_layer_forward(self, x, pts),
-                                                         "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X fused head"})
-    return _fused_cls[base]
+    return _seam.graft(_SEAM, base, {"forward": lambda self, x, pts: gs_layer_forward(self, x, pts)}, "fused head")
 
 
 def fuse_gs_head(renderer):
     """Swap the class of `renderer.gs_net` for fused_gs_layer_cls of its own class: forward_gs then ends in one HIP pass. The module
     object, its parameters and its state dict are untouched. Returns the renderer."""
     net = renderer.gs_net
-    if not is_fused_cls(type(net)) and not isinstance(net, GSLayer):
-        net.__class__ = fused_gs_layer_cls(type(net))
+    if not isinstance(net, GSLayer):
+        _seam.swap(_SEAM, net)
     return renderer

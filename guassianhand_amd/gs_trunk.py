@@ -28,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi, gs_head
+from . import _abi, _seam, gs_head
 from ._call import check_f32, check_ops, cotangent, launch, ptr, row_stride, rows
 from .gs_head import FIELDS, FIXED_WIDTHS, SHS_WIDTHS, check_pts_and_clip, check_widths, gs_head_ref, head_config, head_desc, new_outputs, pack
 from .renderer import GaussianModel
@@ -235,20 +235,15 @@ def forward_gs_fused(renderer, x, p):
     return renderer.gs_net(x, p)
 
 
-_fused_cls = {}
+_SEAM = (__name__, "fused_forward_gs_cls")
 
 
 def fused_forward_gs_cls(base):
     """A subclass of the given renderer class whose forward_gs is forward_gs_fused; everything else stays the base class's."""
-    if base not in _fused_cls:
-        _fused_cls[base] = type(base.__name__, (base,), {"forward_gs": forward_gs_fused, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X fused trunk"})
-    return _fused_cls[base]
+    return _seam.graft(_SEAM, base, {"forward_gs": forward_gs_fused}, "fused trunk")
 
 
 def fuse_forward_gs(renderer):
     """Swap the renderer's class for fused_forward_gs_cls of its own class. Module objects, parameters and the state dict are
     untouched; calling it again changes nothing. Returns the renderer."""
-    if type(renderer) not in _fused_cls.values():
-        renderer.__class__ = fused_forward_gs_cls(type(renderer))
-    return renderer
+    return _seam.swap(_SEAM, renderer)

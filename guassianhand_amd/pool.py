@@ -29,7 +29,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_ops, launch, lib, ptr, row_stride, rows, workspace
 from .cond import PointRows
 
@@ -448,5 +448,4 @@ def fused_pointnet_cls(base):
     parameters and the config handling stay the base class's. `guassianhand_amd.tgs_pointnet.LocalPoolPointnet` is this class
     over tgs.models.pointclouds.pointnet_texture.LocalPoolPointnet (importing the base needs a module named torch_scatter:
     INTEGRATION.md)."""
-    return type(base.__name__, (base,), {"forward": lambda self, p: pointnet_forward(self, p), "__module__": __name__,
-                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X pooling"})
+    return _seam.graft((__name__, "fused_pointnet_cls"), base, {"forward": lambda self, p: pointnet_forward(self, p)}, "pooling")

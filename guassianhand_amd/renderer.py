@@ -19,6 +19,7 @@ from typing import Dict, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
+from . import _seam
 from ._call import launch, lib, ptr
 from .camera import pack_cameras_from_w2c
 from .rasterizer import rasterize_views
@@ -306,8 +307,7 @@ def forward_single_batch_edit(self, gs_hidden_features: torch.Tensor, query_poin
 def fused_renderer_cls_edit(base):
     """fused_renderer_cls for tgs.models.renderer_one_shot_edit.GS3DRenderer (three of the reference's four YAML configs bind it):
     a subclass whose forward_single_batch is forward_single_batch_edit; `guassianhand_amd.tgs_renderer.GS3DRendererEdit`."""
-    return type(base.__name__, (base,), {"forward_single_batch": forward_single_batch_edit, "__module__": __name__,
-                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X forward_single_batch"})
+    return _seam.graft((__name__, "fused_renderer_cls_edit"), base, {"forward_single_batch": forward_single_batch_edit}, "forward_single_batch")
 
 
 def fused_renderer_cls(base):
@@ -315,5 +315,4 @@ def fused_renderer_cls(base):
     tgs/__init__.py:4-9): a subclass of the given `GS3DRenderer` whose forward_single_batch is the composed MI355X path
     above; everything else — configure(), the feature fetch, SelfAttn, the batch loop of forward() (:514-648) — is the
     base class's. `guassianhand_amd.tgs_renderer.GS3DRenderer` is this class over tgs.models.renderer_one_shot.GS3DRenderer."""
-    return type(base.__name__, (base,), {"forward_single_batch": forward_single_batch, "__module__": __name__,
-                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X forward_single_batch"})
+    return _seam.graft((__name__, "fused_renderer_cls"), base, {"forward_single_batch": forward_single_batch}, "forward_single_batch")

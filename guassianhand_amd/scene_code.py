@@ -41,7 +41,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_ops, cotangent, launch, ptr
 
 MAX_CI, MAX_CO = _abi.GH_SCENE_MAX_CI, _abi.GH_SCENE_MAX_CO
@@ -239,17 +239,11 @@ class TriplaneUpsampleNetwork(nn.Module):
         return upsample_ref(self, triplanes) if out is None else out
 
 
-_fused_cls = {}
-
-
 def fused_upsample_cls(base):
     """A subclass of the given class (the reference's own tgs.models.networks_texture.TriplaneUpsampleNetwork) whose forward runs
     the kernel's per-plane form where it applies and the base class's forward, unchanged, everywhere else."""
-    if base not in _fused_cls:
-        def forward(self, triplanes):
-            out = upsample_forward(self, triplanes)
-            return base.forward(self, triplanes) if out is None else out
+    def forward(self, triplanes):
+        out = upsample_forward(self, triplanes)
+        return base.forward(self, triplanes) if out is None else out
 
-        _fused_cls[base] = type(base.__name__, (base,), {"forward": forward, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X upsample kernel"})
-    return _fused_cls[base]
+    return _seam.graft((__name__, "fused_upsample_cls"), base, {"forward": forward}, "upsample kernel")

@@ -25,6 +25,13 @@ def _ensure_torch_scatter():
         sys.modules["torch_scatter"] = shim
 
 
+def _folded(base):
+    from ._seam import graft
+    cls = graft((__name__, "_folded"), base, {"block_ops": "folded"}, doc=f"{base.__name__} with the ResNet blocks folded per cell")
+    cls.__name__ = cls.__qualname__ = "LocalPoolPointnetFolded"                   # the one made class with a name of its own
+    return cls
+
+
 def __getattr__(name):
     if name == "LocalPoolPointnet":
         if name not in _cache:
@@ -35,8 +42,6 @@ def __getattr__(name):
         return _cache[name]
     if name == "LocalPoolPointnetFolded":
         if name not in _cache:
-            base = __getattr__("LocalPoolPointnet")
-            _cache[name] = type(name, (base,), {"block_ops": "folded", "__module__": __name__,
-                                                "__doc__": f"{base.__name__} with the ResNet blocks folded per cell"})
+            _cache[name] = _folded(__getattr__("LocalPoolPointnet"))
         return _cache[name]
     raise AttributeError(name)

@@ -46,7 +46,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_ops, cotangent, launch, lib, ptr, row_stride, rows, workspace
 
 HEAD_DIMS = (32, 64)
@@ -764,14 +764,9 @@ class Transformer1D(nn.Module):
 
 
 # ---- the seam: a built module's forward ------------------------------------------------------------------------------------------------
-_fused_cls = {}
+_SEAM = (__name__, "fused_transformer1d_cls")
 _SEAM_DOC = {"none": "", "input": " and backward to the input",
              "params": " and backward to the input and to every parameter that requires a gradient (gh_xf_backward_params)"}
-
-
-def _new_fused(base, grad="none"):
-    cls = fused_transformer1d_cls(base, grad)
-    return cls.__new__(cls)
 
 
 def fused_transformer1d_cls(base, grad: str = "none"):
@@ -779,32 +774,23 @@ def fused_transformer1d_cls(base, grad: str = "none"):
     own forward, with the caller's arguments, everywhere else. grad="input": the kernels also carry the gradient to the input;
     grad="params": and to every parameter that requires one."""
     _check_grad(grad)
-    if (base, grad) not in _fused_cls:
-        def forward(self, hidden_states, encoder_hidden_states=None, timestep=None, modulation_cond=None, class_labels=None,
-                    cross_attention_kwargs=None, attention_mask=None, encoder_attention_mask=None):
-            # timestep, modulation_cond and class_labels are read by the adaptive norms alone, which kernel_reason refuses: with plain
-            # nn.LayerNorm blocks the base class ignores them (TGS._forward passes modulation_cond to both backbones on every call)
-            masks = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
-            asks = masks if grad == "none" else dict(masks, grad=grad)
-            if not cross_attention_kwargs and kernel_reason(self, hidden_states, **asks) is None:
-                params = params_of(self)
-                return _go(_packed_of(self, params), hidden_states, grad, params)
-            kw = dict(masks, timestep=timestep, modulation_cond=modulation_cond, class_labels=class_labels, cross_attention_kwargs=cross_attention_kwargs)
-            return base.forward(self, hidden_states, **{k: v for k, v in kw.items() if v is not None})
 
-        def reduce_ex(self, protocol):
-            # the class is made at run time and no module attribute names it: a pickle rebuilds it from its base
-            return _new_fused, (base, grad), self.__dict__
+    def forward(self, hidden_states, encoder_hidden_states=None, timestep=None, modulation_cond=None, class_labels=None,
+                cross_attention_kwargs=None, attention_mask=None, encoder_attention_mask=None):
+        # timestep, modulation_cond and class_labels are read by the adaptive norms alone, which kernel_reason refuses: with plain
+        # nn.LayerNorm blocks the base class ignores them (TGS._forward passes modulation_cond to both backbones on every call)
+        masks = dict(encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, encoder_attention_mask=encoder_attention_mask)
+        asks = masks if grad == "none" else dict(masks, grad=grad)
+        if not cross_attention_kwargs and kernel_reason(self, hidden_states, **asks) is None:
+            params = params_of(self)
+            return _go(_packed_of(self, params), hidden_states, grad, params)
+        kw = dict(masks, timestep=timestep, modulation_cond=modulation_cond, class_labels=class_labels, cross_attention_kwargs=cross_attention_kwargs)
+        return base.forward(self, hidden_states, **{k: v for k, v in kw.items() if v is not None})
 
-        doc = f"{base.__module__}.{base.__name__} with the MI355X fused forward" + _SEAM_DOC[grad]
-        _fused_cls[(base, grad)] = type(base.__name__, (base,), {"forward": forward, "__reduce_ex__": reduce_ex, "__module__": __name__,
-                                                                 "__doc__": doc, "_gh_base": base, "_gh_grad": grad})
-    return _fused_cls[(base, grad)]
+    return _seam.graft(_SEAM, base, {"forward": forward, "_gh_grad": grad}, "fused forward" + _SEAM_DOC[grad], options=(grad,))
 
 
 def fuse_transformer1d(module, grad: str = "none"):
     """Swap the module's class for fused_transformer1d_cls of its own class. Module objects, parameters and the state dict are
     untouched; calling it again with the same grad changes nothing, with another it swaps to that class. Returns the module."""
-    base = type(module)._gh_base if type(module) in _fused_cls.values() else type(module)
-    module.__class__ = fused_transformer1d_cls(base, grad)
-    return module
+    return _seam.swap(_SEAM, module, grad)

@@ -27,6 +27,7 @@ plain torch on the gathered rows: O(N) elementwise work that autograd differenti
 `install_livehand_shim()` serves the reference's module-level `from livehand.input_encoder import ...` when livehand is absent."""
 from __future__ import annotations
 
+import functools
 import importlib.util
 import sys
 import types
@@ -242,7 +243,7 @@ def get_uvd(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, face
 def fuse_get_uvd(renderer, **kw):
     """Set `renderer.get_uvd`, the hook renderer.forward_single_batch and forward_single_batch_edit read before they reach for
     livehand. Keywords (split=, ops=) are bound into the hook. Nothing else of the object changes. Returns the renderer."""
-    hook = get_uvd if not kw else (lambda points, verts, faces, face_uv_xy: get_uvd(points, verts, faces, face_uv_xy, **kw))
+    hook = functools.partial(get_uvd, **kw) if kw else get_uvd
     object.__setattr__(renderer, "get_uvd", hook)
     return renderer
 

@@ -33,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, _seam
 from ._call import check_f32, check_ops, cotangent, launch, lib, ptr, row_stride, rows, struct, workspace
 from ._mlp_block import _MLPBlock, block_params, dropout_live, init_linears
 
@@ -216,22 +216,19 @@ class VertPosRefinement(_VertModule):
         self.radius = radius
 
 
-_fused_cls = {}
+_SEAM = (__name__, "fused_vert_cls")
 
 
 def fused_vert_cls(base):
     """A subclass of the given class (the reference's own tgs.models.verts_refinement.vert_valid or vert_pos_refinement) whose forward
     is vert_module_forward while dropout is inactive, and the base class's own forward, unchanged, in train mode with dropout p > 0.
     The activation follows the head: an `fc` with one output is the gate, with three the refinement."""
-    if base not in _fused_cls:
-        def forward(self, verts_f, verts_position):
-            if dropout_live(self, self.ff):
-                return base.forward(self, verts_f, verts_position)
-            return vert_module_forward(self, verts_f, verts_position, "sigmoid" if self.fc.out_features == 1 else "tanh_offset")
+    def forward(self, verts_f, verts_position):
+        if dropout_live(self, self.ff):
+            return base.forward(self, verts_f, verts_position)
+        return vert_module_forward(self, verts_f, verts_position, "sigmoid" if self.fc.out_features == 1 else "tanh_offset")
 
-        _fused_cls[base] = type(base.__name__, (base,), {"forward": forward, "__module__": __name__,
-                                                         "__doc__": f"{base.__module__}.{base.__name__} with the MI355X fused MLP block"})
-    return _fused_cls[base]
+    return _seam.graft(_SEAM, base, {"forward": forward}, "fused MLP block")
 
 
 def fuse_vert_mlps(renderer):
@@ -240,6 +237,6 @@ def fuse_vert_mlps(renderer):
     are untouched. Returns the renderer."""
     for name in ("gs_valid", "vert_pos_refinement"):
         m = getattr(renderer, name)
-        if type(m) not in _fused_cls.values() and not isinstance(m, _VertModule):
-            m.__class__ = fused_vert_cls(type(m))
+        if not isinstance(m, _VertModule):
+            _seam.swap(_SEAM, m)
     return renderer

@@ -229,8 +229,10 @@ def no_livehand():
 
 def test_opt_in_renderer_names_resolve_lazily(no_livehand):
     import guassianhand_amd.tgs_renderer as T
-    assert T._BLOCK == {"FusedAttnBlock": ("FusedAttn", False), "FusedAllFetchAttnBlock": ("FusedAllFetchAttn", False),
-                        "FusedAllFetchAttnBlockUvd": ("FusedAllFetchAttnBlock", True)}
+    assert T._VARIANTS["FusedAttnBlock"] == T._VARIANTS["FusedAttn"] + ("block",) == ("attn", "block")
+    assert T._VARIANTS["FusedAllFetchAttnBlock"] == T._VARIANTS["FusedAllFetchAttn"] + ("block",)
+    assert T._VARIANTS["FusedAllFetchAttnBlockUvd"] == T._VARIANTS["FusedAllFetchAttnBlock"] + ("uvd",)
+    assert all(row.index("attn") < row.index("block") for row in T._VARIANTS.values() if "block" in row)      # the block grafts what the core made
     with pytest.raises(AttributeError):
         T.GS3DRendererFusedGateAttnBlock
     have_reference = importlib.util.find_spec("tgs") is not None

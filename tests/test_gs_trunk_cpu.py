@@ -309,8 +309,10 @@ def test_opt_in_renderer_names_resolve_lazily(no_livehand):
     configure() is the graft; elsewhere resolving them reaches for the reference's classes and for nothing else."""
     import importlib.util
     import guassianhand_amd.tgs_renderer as R
-    assert R._TRUNK == {"FusedTrunk": "", "FusedAllFetchAttnBlockTrunk": "FusedAllFetchAttnBlock",
-                        "FusedAllFetchAttnBlockUvdTrunk": "FusedAllFetchAttnBlockUvd"}
+    for suffix, inner in (("FusedTrunk", ""), ("FusedAllFetchAttnBlockTrunk", "FusedAllFetchAttnBlock"),
+                          ("FusedAllFetchAttnBlockUvdTrunk", "FusedAllFetchAttnBlockUvd")):
+        assert R._VARIANTS[suffix] == R._VARIANTS.get(inner, ()) + ("head", "trunk")          # the fused head, then the trunk over it
+    assert [s for s, row in R._VARIANTS.items() if "trunk" in row] == ["FusedTrunk", "FusedAllFetchAttnBlockTrunk", "FusedAllFetchAttnBlockUvdTrunk"]
     with pytest.raises(AttributeError):
         R.GS3DRendererFusedGateTrunk
     have_reference = importlib.util.find_spec("tgs") is not None

@@ -223,8 +223,9 @@ def test_uv_gradient_comes_from_torch():
 def test_opt_in_renderer_names_resolve_lazily():
     """tgs_renderer's four new names exist beside the old ones and, like them, import nothing of the reference until asked for."""
     import guassianhand_amd.tgs_renderer as T
-    assert [T._SUFFIXES[s][:3] for s in ("FusedHead", "FusedGate", "FusedAll")] == [(False, True, False), (True, False, False), (True, True, False)]
-    assert T._SUFFIXES["FusedFetch"][:3] == (False, False, True) and T._SUFFIXES["FusedAllFetch"][:3] == (True, True, True)
+    assert [T._VARIANTS[s] for s in ("FusedHead", "FusedGate", "FusedAll")] == [("head",), ("gate",), ("gate", "head")]
+    assert T._VARIANTS["FusedFetch"] == ("fetch",) and T._VARIANTS["FusedAllFetch"] == ("gate", "head", "fetch")
+    assert T._GRAFTS["fetch"][:2] == ("plane", "fuse_plane_fetch")
     with pytest.raises(AttributeError):
         T.GS3DRendererFetch
     for name in ("GS3DRendererFusedFetch", "GS3DRendererEditFusedFetch", "GS3DRendererFusedAllFetch", "GS3DRendererEditFusedAllFetch"):

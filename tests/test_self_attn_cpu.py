@@ -228,18 +228,17 @@ def test_c_abi_refuses_bad_arguments_before_any_launch(gh_lib_path):
 
 
 def test_opt_in_renderer_names_resolve_lazily():
-    """tgs_renderer's four new names exist beside the old ones, the table gained one field, and the old rows keep theirs."""
+    """tgs_renderer's four names with the attention core, and no other name, apply it last; the rows without it keep theirs."""
     import guassianhand_amd.tgs_renderer as T
-    assert T._SUFFIXES["FusedAttn"][:4] == (False, False, False, True) and T._SUFFIXES["FusedAllFetchAttn"][:4] == (True, True, True, True)
-    assert all(row[3] is False for s, row in T._SUFFIXES.items() if not s.endswith("Attn"))
-    assert all(len(row) == 5 and isinstance(row[4], str) for row in T._SUFFIXES.values())
+    assert T._VARIANTS["FusedAttn"] == ("attn",) and T._VARIANTS["FusedAllFetchAttn"] == ("gate", "head", "fetch", "attn")
+    assert [s for s, row in T._VARIANTS.items() if row[-1] == "attn"] == ["FusedAttn", "FusedAllFetchAttn"]
+    assert all("attn" not in row for s, row in T._VARIANTS.items() if "Attn" not in s)
+    assert T._GRAFTS["attn"][:2] == ("attention", "fuse_self_attn") and all(len(row) == 3 and isinstance(row[2], str) for row in T._GRAFTS.values())
     with pytest.raises(AttributeError):
         T.GS3DRendererFusedAttnNothing
-    src = open(T.__file__).read()
     import importlib.util
     have_reference = importlib.util.find_spec("tgs") is not None
     for name in ("GS3DRendererFusedAttn", "GS3DRendererEditFusedAttn", "GS3DRendererFusedAllFetchAttn", "GS3DRendererEditFusedAllFetchAttn"):
-        assert name in src
         if not have_reference:                                     # the name is known: resolving it reaches for the reference's classes
             with pytest.raises(ImportError) as e:
                 getattr(T, name)

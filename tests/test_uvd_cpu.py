@@ -233,7 +233,8 @@ def test_fuse_get_uvd_sets_the_hook_forward_single_batch_reads():
 
 def test_opt_in_renderer_names_resolve_lazily(no_livehand):
     import guassianhand_amd.tgs_renderer as T
-    assert T._UVD == {"FusedUvd": "", "FusedAllFetchAttnUvd": "FusedAllFetchAttn"}
+    assert T._VARIANTS["FusedUvd"] == ("uvd",) and T._VARIANTS["FusedAllFetchAttnUvd"] == T._VARIANTS["FusedAllFetchAttn"] + ("uvd",)
+    assert T._GRAFTS["uvd"][:2] == ("uvd", "fuse_get_uvd")
     with pytest.raises(AttributeError):
         T.GS3DRendererFusedGateUvd
     have_reference = importlib.util.find_spec("tgs") is not None
